@@ -28,9 +28,18 @@ process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1) befor
 GPU, and exits with their status; rank 0's child prints the line.  Under torchrun (WORLD_SIZE set) a
 WORLD_SIZE other than --gpus is refused (exit 2).  n_gpus is the process group's size.
 
-Prints one JSON line (rank 0) with the roofline of the dominant kernel (HIP events on the
-library stream over the timed region) and the CPU oracle timed on the host (cpu_baseline: one
-thread, and one process per core of the box's CPU share), measured before the GPU is touched.
+A plain run does what the headline needs and nothing else: it renders the frames, warms up, times the
+--steps steps and prints one JSON line (rank 0) with the headline (value, ms_per_step) and its
+configuration.  --dump-outputs DIR also writes what the last timed step returned to its caller (poses,
+status, inlier and match counts) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+--full adds everything else to the line: the roofline of the dominant kernel (HIP events on the library
+stream over the timed region), the per-kernel breakdown of the last warmup step, the ATE against the
+rendered ground truth, the flag_chain / flag_chain_one / se3_chain_one / se3_chain_one_cfg3 / lowtex legs
+and the CPU oracle timed on the host (cpu_baseline: one thread, and one process per core of the CPU
+share), measured before the GPU is touched.  The legs' own options (--flag-chain-steps, --cpu-seconds,
+--no-kernel-timing, ...) shape a --full run and are ignored without it.
 """
 import argparse
 import json
@@ -112,6 +121,155 @@ def pingpong(g, U):
     return np.where(r < U, r, 2 * U - 2 - r)
 
 
+def roofline_figures(ctx, timings, warm, time_dom, n_match, B, frames_per_step, ms_per_step):
+    """--full: (roofline, extract_stage, kernels_hbm) from the HIP-event times of the timed region (timings: the
+    dominant kernel's launches) and of the last warmup step (warm: every kernel)."""
+    # ---- roofline of the dominant kernel (HIP events on the library stream around its launches in
+    # the timed region; the breakdown of all kernels comes from the warmup steps)
+    f0 = ctx.batch_frame(0)
+    n_kp = len(f0["kps"])
+    pyr_bytes = sum(int(round(640 / 1.2 ** l)) * int(round(480 / 1.2 ** l)) for l in range(8))
+    dom = max(timings.items(), key=lambda kv: kv[1][0]) if timings else ("none", (0.0, 0))
+    name, (ms, launches) = dom
+    avg_ms = ms / max(launches, 1)
+    per_launch_frames = {"k_gray": B, "k_pyramid": B, "k_pyr_tail": B, "k_fast": B, "k_distribute": B, "k_describe": B,
+                         "k_knn2": B - 1, "k_match_gather": B - 1}.get(name, B)
+    # the level blur of levels 1-7 (RGBD_PB_LEVELS = 1 onwards) runs inside the k_fast launch (blur_thread blocks of its grid)
+    fused_blur = name == "k_fast"
+    nbytes = kernel_bytes(name, per_launch_frames, n_kp, n_match, pyr_bytes, 640, 480, fused_blur)
+    bound = "hbm"
+    achieved = nbytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    # measured HBM traffic of the same kernel from the committed rocprofv3 PMC passes (tools/profile.sh
+    # with SERIAL=1: the library runs single-stream, so a dispatch's device-wide TCC counters are its own;
+    # separate FETCH_SIZE and WRITE_SIZE passes, KB per dispatch), bytes per launch.  gfx950 FETCH_SIZE
+    # counts half the bytes of 16-B-per-lane streaming reads (DESIGN.md 'Roofline accounting'): kernels
+    # whose global reads are 16-B/lane get the factor 2, the others (dword loads) are taken as counted.
+    FETCH_16B = {"k_fast": 2.0, "k_pyramid": 2.0}
+    traffic = None
+    valu = None
+    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
+    if os.path.exists(pmc_path):
+        pmc = json.load(open(pmc_path)).get(name, {})
+        if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+            traffic = int((FETCH_16B.get(name, 1.0) * pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024)
+        # the bound this path actually has: VALU issue.  SQ_INSTS_VALU (wave64 instructions per launch, same
+        # PMC pass set) priced three ways against the chip's issue capacity (1024 SIMDs x 2.4 GHz cycles):
+        #   at_2cyc   every instruction at the 2-cycle best case (78.6 T lane-ops/s);
+        #   priced    at the measured per-class issue costs (profiles/r02_ubench/valu_rate.txt) weighted by the
+        #             kernel's static VALU mix (tools/valu_mix.py -> profiles/valu_mix.json);
+        #   busy      SQ_ACTIVE_INST_VALU x 4 (quad-cycles -> cycles) / SIMD-cycles: the measured VALU busy.
+        if "SQ_INSTS_VALU" in pmc and avg_ms > 0:
+            ninst = pmc["SQ_INSTS_VALU"]
+            simd_cycles = 1024 * 2.4e9 * avg_ms * 1e-3
+            a_t = ninst * 64 / (avg_ms * 1e-3) / 1e12
+            valu = {"achieved": round(a_t, 3), "peak": VALU_PEAK_TOPS, "unit": "T lane-ops/s",
+                    "frac": round(a_t / VALU_PEAK_TOPS, 4), "insts_per_launch": int(ninst),
+                    "frac_at_2cyc": round(ninst * 2.0 / simd_cycles, 4),
+                    "source": "profiles/pmc_latest.json SQ_INSTS_VALU / HIP-event launch time"}
+            mix_path = os.path.join(ROOT, "profiles", "valu_mix.json")
+            if os.path.exists(mix_path):
+                mix = json.load(open(mix_path)).get(name)
+                if mix:
+                    valu["cyc_per_inst_priced"] = mix["cycles_per_inst"]
+                    valu["frac_priced"] = round(ninst * mix["cycles_per_inst"] / simd_cycles, 4)
+                    valu["priced_source"] = "profiles/valu_mix.json (static VALU mix x valu_rate.txt)"
+            if "SQ_ACTIVE_INST_VALU" in pmc:
+                valu["busy_frac"] = round(pmc["SQ_ACTIVE_INST_VALU"] * 4 / simd_cycles, 4)
+                valu["busy_cyc_per_inst"] = round(pmc["SQ_ACTIVE_INST_VALU"] * 4 / ninst, 3)
+    roofline = {"bound": bound, "kernel": name, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic,
+                "algorithmic_bytes": int(nbytes), "avg_launch_ms": round(avg_ms, 5), "launches": launches,
+                "traffic_source": ("profiles/pmc_latest.json (rocprofv3 serial pass, %s x FETCH_SIZE + WRITE_SIZE)"
+                                   % FETCH_16B.get(name, 1.0)) if traffic else None,
+                "valu": valu, "fused_blur": fused_blur,
+                "time_dominant": ({"kernel": time_dom[0], "ms_warmup_step": round(time_dom[1][0], 4),
+                                   "launches": time_dom[1][1],
+                                   "bound": ("HBM / VALU issue (the roofline kernel)" if time_dom[0] == name else
+                                             "latency: dependent per-pair chains (no byte roofline)")}
+                                  if time_dom else None)}
+    # step level (SURVEY s8d algorithmic bytes per frame: extract BGR + depth in, KeyPoints + descriptors + xyz
+    # out; match 2 N 32 + M 16; solve M (2 12 + 16)) over the measured step time: the whole path's HBM fraction
+    step_bpf = (921600 + 614400 + n_kp * (28 + 32 + 12)) + (2 * n_kp * 32 + n_match * 16) + n_match * 40
+    # the roofline's bound: VALU issue when the measured VALU busy share exceeds the HBM fraction
+    if valu and valu.get("busy_frac", 0.0) > roofline["frac"]:
+        roofline["bound"] = "valu"
+    # the same kernel time priced with the s8d bytes per frame (the path's algorithmic bytes, not the kernel's own)
+    if avg_ms > 0:
+        g8 = step_bpf * per_launch_frames / (avg_ms * 1e-3) / 1e9
+        roofline["s8d"] = {"bytes_per_frame": int(step_bpf), "achieved": round(g8, 3), "frac": round(g8 / HBM_PEAK_GBPS, 6),
+                           "definition": "SURVEY s8d bytes per frame x frames per launch / the kernel's launch time"}
+    step_gbps = step_bpf * frames_per_step / (ms_per_step * 1e-3) / 1e9
+    roofline["step"] = {"bytes_per_frame": int(step_bpf), "achieved": round(step_gbps, 3), "peak": HBM_PEAK_GBPS,
+                        "unit": "GB/s", "frac": round(step_gbps / HBM_PEAK_GBPS, 6),
+                        "definition": "SURVEY s8d bytes per frame x frames per step / ms_per_step (all GPUs)"}
+    # extract stage as a whole (SURVEY s8d: 1,608,000 B/frame at 1000 kp)
+    wsteps = 1
+    ext_ms = sum(v[0] for k, v in warm.items() if k in ("k_gray", "k_pyramid", "k_pyr_tail", "k_fast", "k_distribute",
+                                                        "k_describe", "k_undistort", "k_svo_pyramid",
+                                                        "k_svo_detect", "k_svo_select", "k_svo_brief"))
+    ext_per_frame = 921600 + 614400 + n_kp * (28 + 32 + 12)
+    extract_stage = {"frames": B * wsteps, "kernel_ms": round(ext_ms, 3), "source": "last warmup step, all kernels timed",
+                     "achieved_GBps": round(ext_per_frame * B * wsteps / (ext_ms * 1e-3) / 1e9, 2) if ext_ms else 0,
+                     "frames_per_s_kernel_time": round(B * wsteps / (ext_ms * 1e-3), 1) if ext_ms else 0}
+
+    # every extraction kernel's HBM fraction from the last warmup step (synchronous, one event pair per
+    # launch, so each kernel's time is its own): algorithmic bytes as above / its event time
+    kernels_hbm = {}
+    for k in ("k_pyramid", "k_pyr_tail", "k_fast", "k_distribute", "k_describe", "k_undistort", "k_knn2", "k_match_gather"):
+        if k in warm and warm[k][0] > 0:
+            kb = kernel_bytes(k, {"k_knn2": B - 1, "k_match_gather": B - 1}.get(k, B), n_kp, n_match, pyr_bytes,
+                              640, 480, k == "k_fast")
+            g = kb / (warm[k][0] * 1e-3) / 1e9
+            kernels_hbm[k] = {"ms": warm[k][0], "algorithmic_bytes": int(kb), "GBps": round(g, 1),
+                              "frac": round(g / HBM_PEAK_GBPS, 4), "bytes_kind": KERNEL_BYTES_KIND.get(k, "s8d")}
+    return roofline, extract_stage, kernels_hbm
+
+
+def cpu_share():
+    """(cores this process may use, affinity mask size): on a shared multi-GPU host OMP_NUM_THREADS holds one
+    GPU's share of the cores (16 when unset), while the affinity mask and os.cpu_count() show the whole machine."""
+    try:
+        affinity = len(os.sched_getaffinity(0))
+    except AttributeError:
+        affinity = os.cpu_count() or 1
+    return min(affinity, int(os.environ.get("OMP_NUM_THREADS", "16") or 16)), affinity
+
+
+def _render_part(a):
+    import synth
+    n, seed, preset, start = a
+    return synth.sequence(n, seed=seed, preset=preset, start=start)[:2]
+
+
+def render_sequence(n, seed, preset):
+    """synth.sequence(n, seed, preset), its frames rendered by one process per core of the CPU share (a frame
+    depends on (seed, frame index) alone, so the bytes are those of the serial call).  Forks: call it before
+    anything initialises the GPU."""
+    import multiprocessing as mp
+    import synth
+    P = max(1, min(cpu_share()[0] // int(os.environ.get("LOCAL_WORLD_SIZE", "1")), 16, n))   # the ranks share the cores
+    if P == 1:
+        return synth.sequence(n, seed=seed, preset=preset)
+    cuts = [n * k // P for k in range(P + 1)]
+    with mp.get_context("fork").Pool(P) as pool:
+        parts = pool.map(_render_part, [(cuts[k + 1] - cuts[k], seed, preset, cuts[k]) for k in range(P)])
+    bgr = np.concatenate([p[0] for p in parts])
+    depth = np.concatenate([p[1] for p in parts])
+    return bgr, depth, synth.trajectory(n, seed), dict(synth.PRESETS[preset])
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 stays float64)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, total
+
+
 
 _CPU = {}   # inputs of the CPU legs (set before the pool forks; workers read them)
 
@@ -173,13 +331,7 @@ def cpu_baseline(bgr, depth, cam, args):
         return 1.0 / (te / nfr + tc / max(kc - 1, 1))
 
     single = _cpu_leg(0)
-    try:
-        affinity = len(os.sched_getaffinity(0))
-    except AttributeError:
-        affinity = os.cpu_count() or 1
-    # the GPU box's CPU share for one GPU is 16 cores (OMP_NUM_THREADS there); its affinity mask and
-    # os.cpu_count() show the whole machine
-    share = min(affinity, int(os.environ.get("OMP_NUM_THREADS", "16") or 16))
+    share, affinity = cpu_share()
     P = max(1, min(share, 16))
     _CPU["sec"] = args.cpu_seconds * 0.6
     t0 = time.perf_counter()
@@ -254,6 +406,12 @@ def main():
                     help="process group of N > 1 (nccl = RCCL over xGMI; gloo: CPU pose gather, e.g. ranks sharing a card)")
     ap.add_argument("--steps", type=int, default=200)   # ~1.2 s timed at B = 1024
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: cpu_baseline, the flag_chain / se3_chain_one / cfg3 / lowtex legs, the "
+                         "per-kernel breakdown, the roofline and the ATE (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses, status, n_inliers, n_matches) to "
+                         "DIR/<name>.npy as float32 (rank 0)")
     ap.add_argument("--batch", type=int, default=1024,
                     help="frames per rank per step (64 .. 1024 measured; 1024 best, 512 within 2 %%)")
     ap.add_argument("--unique", type=int, default=64,
@@ -310,6 +468,10 @@ def main():
     if env_world is not None and int(env_world) != args.gpus:
         print(f"bench.py: WORLD_SIZE={env_world} but --gpus {args.gpus}", file=sys.stderr)
         sys.exit(2)
+    if not args.full:   # a plain run: the headline alone (no CPU legs, no further legs, no kernel events)
+        args.no_cpu_baseline = args.no_kernel_timing = True
+        args.flag_chain_steps = args.flag_chain_one_steps = args.se3_chain_one_steps = 0
+        args.cfg3_chain_steps = args.lowtex_steps = 0
     if args.lanes <= 0:   # one pipelined context for pnp; 64 device lanes for the se3 chain
         args.lanes = 64 if args.solver == "se3" else 1
 
@@ -333,7 +495,7 @@ def main():
     src = pingpong(np.arange(n_global), U)
     need = src[lo:hi]
     n_render = int(src.max()) + 1 if (args.posegraph and rank == 0) else int(need.max()) + 1
-    ub, ud, ut, cam = synth.sequence(n_render, seed=seq_seed, preset=args.preset)
+    ub, ud, ut, cam = render_sequence(n_render, seq_seed, args.preset)
     gt_all = synth.trajectory(U, seed=seq_seed)[src]
     pose0 = gt_all[lo].astype(np.float32) if (rank == 0 or args.mode == "sequences") else np.eye(4, dtype=np.float32)
 
@@ -341,12 +503,12 @@ def main():
     U3 = 16
     if args.cfg3_chain_steps > 0:
         src3 = pingpong(np.arange(B), U3)
-        ub3, ud3, _, cam3 = synth.sequence(U3, seed=3000 + 7919 * rank, preset="fr2")
+        ub3, ud3, _, cam3 = render_sequence(U3, 3000 + 7919 * rank, "fr2")
 
     # the low-texture leg's frames (fr1 camera, the headline context's): rendered here like the headline's
     do_lowtex = args.lowtex_steps > 0 and args.solver == "pnp" and args.extractor == "orb" and args.preset == "fr1"
     if do_lowtex:
-        ubl, udl, _, _ = synth.sequence(min(U, 16), seed=seq_seed + 17, preset="lowtex")
+        ubl, udl, _, _ = render_sequence(min(U, 16), seq_seed + 17, "lowtex")
         srcl = pingpong(np.arange(nb), min(U, 16))
 
     # ---- CPU baseline first: the oracle on the host cores, before anything initialises the GPU
@@ -386,7 +548,9 @@ def main():
     rng = pkg.rng(1234 + rank)
     sticky = pkg.Sticky()
     PAD = B + 1
-    last = {}
+    import threading
+    last = {}                  # the newest step's outputs
+    mine = threading.local()   # ... of the calling thread's newest step (the se3 contexts step from their own threads)
     if world > 1:   # the hand-off buffers: a pinned host block, its device copy, the gathered blocks
         pad_h = torch.zeros((PAD, 16), dtype=torch.float32, pin_memory=coll_dev.type == "cuda")
         pad_d = torch.zeros((PAD, 16), dtype=torch.float32, device=coll_dev)
@@ -395,7 +559,8 @@ def main():
     def finish(poses, status, ninl):
         # every rank keeps its chunk's poses; the PoseGraph hand-off gathers them once, after the timed region
         # (north_star: "RCCL all-gather of poses ... only for the final PoseGraph hand-off")
-        last["poses"] = poses.reshape(nb, 16)
+        mine.out = {"poses": poses.reshape(nb, 16), "status": status, "ninl": ninl}
+        last.update(mine.out)
         return status, ninl
 
     def hand_off():
@@ -414,7 +579,6 @@ def main():
         lane_rng = [[pkg.rng(1234 + 4096 * rank + 64 * 4096 * k + l) for l in range(args.lanes)] for k in range(n_ctx)]
         lane_st = [[pkg.Sticky() for _ in range(args.lanes)] for k in range(n_ctx)]
 
-    import threading
     ext_lock = threading.Lock()
     round_streams, ext_stream = [], None
     if se3_lanes and n_ctx > 1 and args.se3_priority:
@@ -488,22 +652,26 @@ def main():
         library calls release the GIL), so their device work overlaps."""
         import concurrent.futures as cf
         out = [None] * steps
+        final = {}
 
         def worker(k):
             for i in range(k, steps, L):
                 ts = time.perf_counter()
                 status, ninl = step(k, split=True)
                 out[i] = (int(status.sum()), float(ninl[1:].mean()), time.perf_counter() - ts)
+                if i == steps - 1:
+                    final.update(mine.out)
         with cf.ThreadPoolExecutor(max_workers=L) as ex:
             for f in [ex.submit(worker, k) for k in range(L)]:
                 f.result()
+        last.update(final)   # the last step's outputs, whichever thread finished last
         return out
 
     for i in range(nw):
-        if i == nw - 1:   # the last warmup step (warm caches) is the one every kernel is timed in
+        if i == nw - 1:   # the last warmup step (warm caches) is the one every kernel is timed in (--full)
             torch.cuda.synchronize()
             ctx.reset_timing()
-            ctx.set_timing(True)
+            ctx.set_timing(args.full)
             step()
         elif pipelined:
             run_pipelined(per_ctx_depth * L, pnp_prm, per_ctx_depth)
@@ -556,9 +724,14 @@ def main():
     t_h = time.perf_counter()
     hand_off()   # outside the timed region: the gather of the last step's poses for the PoseGraph
     hand_off_ms = (time.perf_counter() - t_h) * 1e3
+    if args.dump_outputs and rank == 0:   # what the last timed step returned to its caller (rank 0's chunk)
+        arrays = {"poses": last["poses"], "status": last["status"], "n_inliers": last["ninl"]}
+        if "nm" in last:
+            arrays["n_matches"] = last["nm"]
+        dump_outputs(args.dump_outputs, arrays)
     traj = None
     ate_m = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.posegraph):
         allp = last["allp"]
         allp = allp.cpu().numpy() if hasattr(allp, "cpu") else allp
         # chunks: the stitched sequence; sequences: rank 0's own (every rank's poses were gathered)
@@ -704,106 +877,12 @@ def main():
     value = frames_total / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
 
-    # ---- roofline of the dominant kernel (HIP events on the library stream around its launches in
-    # the timed region; the breakdown of all kernels comes from the warmup steps)
-    n_kp = ctx.kp_cap  # upper bound; replaced by the measured mean below
-    f0 = ctx.batch_frame(0)
-    n_kp = len(f0["kps"])
-    pyr_bytes = sum(int(round(640 / 1.2 ** l)) * int(round(480 / 1.2 ** l)) for l in range(8))
-    dom = max(timings.items(), key=lambda kv: kv[1][0]) if timings else ("none", (0.0, 0))
-    name, (ms, launches) = dom
-    avg_ms = ms / max(launches, 1)
     n_match = int(np.mean(last["nm"][1:])) if "nm" in last else 600
-    per_launch_frames = {"k_gray": B, "k_pyramid": B, "k_pyr_tail": B, "k_fast": B, "k_distribute": B, "k_describe": B,
-                         "k_knn2": B - 1, "k_match_gather": B - 1}.get(name, B)
-    # the level blur of levels 1-7 (RGBD_PB_LEVELS = 1 onwards) runs inside the k_fast launch (blur_thread blocks of its grid)
-    fused_blur = name == "k_fast"
-    nbytes = kernel_bytes(name, per_launch_frames, n_kp, n_match, pyr_bytes, 640, 480, fused_blur)
-    bound = "hbm"
-    achieved = nbytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # measured HBM traffic of the same kernel from the committed rocprofv3 PMC passes (tools/profile.sh
-    # with SERIAL=1: the library runs single-stream, so a dispatch's device-wide TCC counters are its own;
-    # separate FETCH_SIZE and WRITE_SIZE passes, KB per dispatch), bytes per launch.  gfx950 FETCH_SIZE
-    # counts half the bytes of 16-B-per-lane streaming reads (MI355X_MICROARCH.md, HBM section): kernels
-    # whose global reads are 16-B/lane get the factor 2, the others (dword loads) are taken as counted.
-    FETCH_16B = {"k_fast": 2.0, "k_pyramid": 2.0}
-    traffic = None
-    valu = None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    if os.path.exists(pmc_path):
-        pmc = json.load(open(pmc_path)).get(name, {})
-        if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-            traffic = int((FETCH_16B.get(name, 1.0) * pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024)
-        # the bound this path actually has: VALU issue.  SQ_INSTS_VALU (wave64 instructions per launch, same
-        # PMC pass set) priced three ways against the chip's issue capacity (1024 SIMDs x 2.4 GHz cycles):
-        #   at_2cyc   every instruction at the 2-cycle best case (78.6 T lane-ops/s);
-        #   priced    at the measured per-class issue costs (profiles/r02_ubench/valu_rate.txt) weighted by the
-        #             kernel's static VALU mix (tools/valu_mix.py -> profiles/valu_mix.json);
-        #   busy      SQ_ACTIVE_INST_VALU x 4 (quad-cycles -> cycles) / SIMD-cycles: the measured VALU busy.
-        if "SQ_INSTS_VALU" in pmc and avg_ms > 0:
-            ninst = pmc["SQ_INSTS_VALU"]
-            simd_cycles = 1024 * 2.4e9 * avg_ms * 1e-3
-            a_t = ninst * 64 / (avg_ms * 1e-3) / 1e12
-            valu = {"achieved": round(a_t, 3), "peak": VALU_PEAK_TOPS, "unit": "T lane-ops/s",
-                    "frac": round(a_t / VALU_PEAK_TOPS, 4), "insts_per_launch": int(ninst),
-                    "frac_at_2cyc": round(ninst * 2.0 / simd_cycles, 4),
-                    "source": "profiles/pmc_latest.json SQ_INSTS_VALU / HIP-event launch time"}
-            mix_path = os.path.join(ROOT, "profiles", "valu_mix.json")
-            if os.path.exists(mix_path):
-                mix = json.load(open(mix_path)).get(name)
-                if mix:
-                    valu["cyc_per_inst_priced"] = mix["cycles_per_inst"]
-                    valu["frac_priced"] = round(ninst * mix["cycles_per_inst"] / simd_cycles, 4)
-                    valu["priced_source"] = "profiles/valu_mix.json (static VALU mix x valu_rate.txt)"
-            if "SQ_ACTIVE_INST_VALU" in pmc:
-                valu["busy_frac"] = round(pmc["SQ_ACTIVE_INST_VALU"] * 4 / simd_cycles, 4)
-                valu["busy_cyc_per_inst"] = round(pmc["SQ_ACTIVE_INST_VALU"] * 4 / ninst, 3)
-    roofline = {"bound": bound, "kernel": name, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic,
-                "algorithmic_bytes": int(nbytes), "avg_launch_ms": round(avg_ms, 5), "launches": launches,
-                "traffic_source": ("profiles/pmc_latest.json (rocprofv3 serial pass, %s x FETCH_SIZE + WRITE_SIZE)"
-                                   % FETCH_16B.get(name, 1.0)) if traffic else None,
-                "valu": valu, "fused_blur": fused_blur,
-                "time_dominant": ({"kernel": time_dom[0], "ms_warmup_step": round(time_dom[1][0], 4),
-                                   "launches": time_dom[1][1],
-                                   "bound": ("HBM / VALU issue (the roofline kernel)" if time_dom[0] == name else
-                                             "latency: dependent per-pair chains (no byte roofline)")}
-                                  if time_dom else None)}
-    # step level (SURVEY s8d algorithmic bytes per frame: extract BGR + depth in, KeyPoints + descriptors + xyz
-    # out; match 2 N 32 + M 16; solve M (2 12 + 16)) over the measured step time: the whole path's HBM fraction
-    step_bpf = (921600 + 614400 + n_kp * (28 + 32 + 12)) + (2 * n_kp * 32 + n_match * 16) + n_match * 40
-    # the roofline's bound: VALU issue when the measured VALU busy share exceeds the HBM fraction
-    if valu and valu.get("busy_frac", 0.0) > roofline["frac"]:
-        roofline["bound"] = "valu"
-    # the same kernel time priced with the s8d bytes per frame (the path's algorithmic bytes, not the kernel's own)
-    if avg_ms > 0:
-        g8 = step_bpf * per_launch_frames / (avg_ms * 1e-3) / 1e9
-        roofline["s8d"] = {"bytes_per_frame": int(step_bpf), "achieved": round(g8, 3), "frac": round(g8 / HBM_PEAK_GBPS, 6),
-                           "definition": "SURVEY s8d bytes per frame x frames per launch / the kernel's launch time"}
-    step_gbps = step_bpf * (n_global if args.mode == "chunks" else world * B) / (ms_per_step * 1e-3) / 1e9
-    roofline["step"] = {"bytes_per_frame": int(step_bpf), "achieved": round(step_gbps, 3), "peak": HBM_PEAK_GBPS,
-                        "unit": "GB/s", "frac": round(step_gbps / HBM_PEAK_GBPS, 6),
-                        "definition": "SURVEY s8d bytes per frame x frames per step / ms_per_step (all GPUs)"}
-    # extract stage as a whole (1,608,000 B/frame at 1000 kp)
-    wsteps = 1
-    ext_ms = sum(v[0] for k, v in warm.items() if k in ("k_gray", "k_pyramid", "k_pyr_tail", "k_fast", "k_distribute",
-                                                        "k_describe", "k_undistort", "k_svo_pyramid",
-                                                        "k_svo_detect", "k_svo_select", "k_svo_brief"))
-    ext_per_frame = 921600 + 614400 + n_kp * (28 + 32 + 12)
-    extract_stage = {"frames": B * wsteps, "kernel_ms": round(ext_ms, 3), "source": "last warmup step, all kernels timed",
-                     "achieved_GBps": round(ext_per_frame * B * wsteps / (ext_ms * 1e-3) / 1e9, 2) if ext_ms else 0,
-                     "frames_per_s_kernel_time": round(B * wsteps / (ext_ms * 1e-3), 1) if ext_ms else 0}
-
-    # every extraction kernel's HBM fraction from the last warmup step (synchronous, one event pair per
-    # launch, so each kernel's time is its own): algorithmic bytes as above / its event time
-    kernels_hbm = {}
-    for k in ("k_pyramid", "k_pyr_tail", "k_fast", "k_distribute", "k_describe", "k_undistort", "k_knn2", "k_match_gather"):
-        if k in warm and warm[k][0] > 0:
-            kb = kernel_bytes(k, {"k_knn2": B - 1, "k_match_gather": B - 1}.get(k, B), n_kp, n_match, pyr_bytes,
-                              640, 480, k == "k_fast")
-            g = kb / (warm[k][0] * 1e-3) / 1e9
-            kernels_hbm[k] = {"ms": warm[k][0], "algorithmic_bytes": int(kb), "GBps": round(g, 1),
-                              "frac": round(g / HBM_PEAK_GBPS, 4), "bytes_kind": KERNEL_BYTES_KIND.get(k, "s8d")}
+    roofline = extract_stage = kernels_hbm = None
+    if args.full:
+        roofline, extract_stage, kernels_hbm = roofline_figures(ctx, timings, warm, time_dom, n_match, B,
+                                                                n_global if args.mode == "chunks" else world * B,
+                                                                ms_per_step)
 
     # ---- the low-texture regime beside the headline: the same pipelined chain on frames where FAST at 20 finds
     # almost nothing and the per-cell minThFAST = 7 fallback decides (Features/ORBextractor.cpp:655-661)
@@ -849,7 +928,7 @@ def main():
             "value": round(value, 2), "unit": "frames/s", "n_gpus": dist.get_world_size() if dist is not None else 1, "steps": args.steps,
             "warmup": nw, "ms_per_step": round(ms_per_step, 3),
             "ms_per_step_median": round(float(np.median(step_s)) * 1e3, 3) if step_s else None,
-            "higher_is_better": True,
+            "higher_is_better": True, "full": args.full,   # without --full: the sections below the hand-off are null
             "scaling": "weak", "vs_baseline": None, "dtype": "u8/i32 (fp32+fp64 solver)",
             "data": (f"synthetic (tools/synth.py, seeded {args.preset}-camera RGB-D, 640x480; {U} rendered frames "
                      "walked back and forth to fill the batch, each slot its own HBM copy)"),

@@ -6,6 +6,7 @@ TAG=$1; VAR=$2; A=$3; B=$4; N=${5:-2}; shift 5 || shift $#
 [ "$1" == "--" ] && shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$R/gpurun_out/$TAG"
+set -- --full "$@"   # the per-kernel breakdown printed below belongs to a --full run
 for i in $(seq 1 $N); do
   for v in $A $B; do
     env $VAR=$v timeout -k 10 240 python3 -u "$R/bench.py" --no-cpu-baseline --flag-chain-steps 0 --flag-chain-one-steps 0 "$@" > "$R/gpurun_out/$TAG/$VAR-$v-$i.log" 2>&1 || { echo "$VAR=$v failed rc=$?"; exit 1; }

@@ -10,7 +10,7 @@ timeout -k 10 400 python3 -u -m pytest ${TESTS:-tests/test_gpu_extract.py tests/
 tail -1 "$O/tests.log"
 cd /tmp && export TMPDIR=/tmp
 for lib in ${LIBS:-build}; do
-  RGBD_HIP_LIB=$R/rgbd-slam_amd/$lib/librgbd_hip.so timeout -k 10 170 rocprofv3 --kernel-trace --stats -d "$O/$lib" -o run --output-format csv -- python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --flag-chain-steps 0 --flag-chain-one-steps 0 --lowtex-steps 0 > "$O/$lib.log" 2>&1 || exit 1
+  RGBD_HIP_LIB=$R/rgbd-slam_amd/$lib/librgbd_hip.so timeout -k 10 170 rocprofv3 --kernel-trace --stats -d "$O/$lib" -o run --output-format csv -- python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --flag-chain-steps 0 --flag-chain-one-steps 0 --lowtex-steps 0 > "$O/$lib.log" 2>&1 || exit 1
   rm -f "$O/$lib/run_kernel_trace.csv"
 done
 cd "$R" && LIBS="${LIBS:-build}" bash tools/se3_check.sh "$TAG" "$RUNS"

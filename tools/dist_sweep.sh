@@ -18,7 +18,7 @@ for rep in 1 2; do
   i=0
   for sh in "$@"; do
     i=$((i+1)); e=${sh/#-/}
-    env $e timeout -k 10 200 python3 -u bench.py --no-cpu-baseline --flag-chain-steps 0 --flag-chain-one-steps 0 > "$O/bench_${i}_$rep.log" 2>&1 || { echo "bench [$sh] failed"; tail -20 "$O/bench_${i}_$rep.log"; exit 1; }
+    env $e timeout -k 10 200 python3 -u bench.py --full --no-cpu-baseline --flag-chain-steps 0 --flag-chain-one-steps 0 > "$O/bench_${i}_$rep.log" 2>&1 || { echo "bench [$sh] failed"; tail -20 "$O/bench_${i}_$rep.log"; exit 1; }
     python3 -c "import json,sys;d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]);print(sys.argv[2],d['value'],d['ms_per_step_median'],{k:v[0] for k,v in d['kernels_ms_warmup'].items() if v[0]>0.1})" "$O/bench_${i}_$rep.log" "[$sh]"
   done
 done

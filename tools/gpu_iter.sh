@@ -9,7 +9,7 @@ mkdir -p "$O"
 cd "$R"
 timeout -k 10 400 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > "$O/gputest.log" 2>&1
 echo "tests: $(tail -1 "$O/gputest.log")"
-timeout -k 10 200 python3 -u bench.py --no-cpu-baseline "$@" > "$O/bench.log" 2>&1
+timeout -k 10 200 python3 -u bench.py --full --no-cpu-baseline "$@" > "$O/bench.log" 2>&1
 tail -1 "$O/bench.log" > "$O/bench.json"
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('bench', d['value'], d['ms_per_step'], d['ms_per_step_median'], {k: v[0] for k, v in d['kernels_ms_warmup'].items()})" "$O/bench.json"
 "$R/tools/pmc_quick.sh" "$TAG/pmc" "$@"

@@ -6,6 +6,7 @@ TAG=$1; shift
 V=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do V+=("$1"); shift; done; [ "$1" == "--" ] && shift
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$R/gpurun_out/$TAG"
+set -- --full "$@"   # the per-kernel breakdown printed below belongs to a --full run
 for v in "${V[@]}"; do
   lib="$R/rgbd-slam_amd/$v/librgbd_hip.so"
   RGBD_HIP_LIB=$lib timeout -k 10 240 python3 -u "$R/bench.py" --no-cpu-baseline --flag-chain-steps 0 "$@" > "$R/gpurun_out/$TAG/$v.log" 2>&1 || { echo "variant $v failed rc=$?"; exit 1; }
