@@ -23,6 +23,7 @@
 #include "dispatch.h"
 
 #include "rgbd_internal.h"
+#include "wave_dev.h"
 
 namespace rgbd {
 
@@ -1027,16 +1028,10 @@ __device__ __forceinline__ int quad_in(int kx, int ky, const int16_t* bx, int nd
                    (int16_t)(bb >> 48));
 }
 
-// ordering of LDS traffic among the lanes of one wave
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Wave scans by DPP (GFX9 row_shr / row_bcast moves, every lane of the wave active): one VALU per step
 // instead of a ds_bpermute round trip.  The moves stay v_mov_b32_dpp (the empty asm, as in fast_rank16).
+// Deliberately separate from wave_dev.h's wave_incl_scan: either form in the other's place compiles k_distribute
+// (or the lane / svo kernels) to different instructions.
 __device__ __forceinline__ int dpp_add(int x, int t)
 {
     asm volatile("" : "+v"(t));

@@ -88,6 +88,8 @@ __device__ inline void sample_hyps(const LaneBufs& lb, const LaneCfg& lc, int l,
 // The phase that completes a lane's pair writes its result and, unless the second reference runs next round,
 // moves the lane to the next frame.  Run by every thread of the calling workgroup (k_lane_replay's one wave, or
 // the last-finishing k_ransac_hyp_lanes workgroup of the lane); the work is wave 0's, the barriers everyone's.
+// Rule: every store to lb.ctl[l] comes after a barrier that follows the entry reads (b, end, need_more, retry, m),
+// so the early returns are workgroup-uniform and no wave skips a barrier the others wait at.
 __device__ inline void lane_replay(const LaneBufs& lb, const LaneCfg& lc, int l, int phase)
 {
     __shared__ int s_best, s_ok, s_n, s_hit, s_hyps, s_calls;
@@ -155,10 +157,10 @@ __device__ inline void lane_replay(const LaneBufs& lb, const LaneCfg& lc, int l,
         s_n = nin;
         s_rmse = rmse;
         s_hit = need ? 1 : 0;
-        if (need) c.need_more = phase + 1;
     }
     if (tid == 0 && (c.early || s_hit)) s_calls = 0;
     __syncthreads();
+    if (tid == 0 && s_hit) c.need_more = phase + 1;   // every thread has done its entry reads (nothing below reads it)
     if (!w0) {
     } else if (s_hit) {   // sampleMatches for the next chunk's hypotheses, continuing the sampler's RNG (whole wave)
         const int h0 = phase == 0 ? lc.e0 : lc.e1, h1 = phase == 0 ? min(lc.e1, c.H) : c.H;

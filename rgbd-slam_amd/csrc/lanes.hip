@@ -25,6 +25,7 @@
 
 #include "lanes_dev.h"
 #include "lane_replay_dev.h"
+#include "wave_dev.h"
 
 #include <cstdio>
 #include <cstring>
@@ -45,18 +46,6 @@ namespace rgbd {
 
 namespace {
 
-// inclusive wave64 scan on DPP (row_shr 1/2/4/8 within 16-lane rows, then row_bcast 15 / 31)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-
 // the minimum over the wave (wave-uniform): an inclusive min scan on DPP (lanes without a source see INT_MAX),
 // read from lane 63 -- six VALU steps instead of six dependent ds_bpermute round trips
 __device__ __forceinline__ int wave_min_i(int v)
@@ -68,13 +57,6 @@ __device__ __forceinline__ int wave_min_i(int v)
     v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 into rows 1, 3
     v = min(v, __builtin_amdgcn_update_dpp(INT_MAX, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 into rows 2, 3
     return __builtin_amdgcn_readlane(v, 63);
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---------------------------------------------------------------- std::sort of the matches by distance

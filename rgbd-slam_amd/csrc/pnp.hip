@@ -24,6 +24,8 @@
 
 #include "pnp_dev.h"
 #include "exact_dev.h"
+#include "gn6_dev.h"
+#include "wave_dev.h"
 
 namespace rgbd {
 
@@ -575,14 +577,6 @@ __device__ __forceinline__ double dpp_row_shr(double x)
     return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
-// ordering of LDS traffic between the lanes of one wave (the workgroup is one wave)
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // EPnP of the hypothesis of one G-lane group (G = kGroup: lane g owns row g; G = kBlkGroup: the block layout
 // of the Jacobi, BlkTab), then its inlier count over the problem's
 // points: *good_dst = count or -1 (no model), model_dst[0..11] = R (row-major), t.  Every lane of the
@@ -660,7 +654,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
 #pragma unroll
             for (int j = 0; j < 3; j++) s.cw[3 * i + j] = cw[i][j];
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(1);
     const bool ok0 = s.ok != 0;
 
@@ -680,7 +674,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                 T1[e] = c == 0 ? al * K.fu : (c == 1 ? 0.0 : al * (K.uc - u));
                 T2[e] = c == 0 ? 0.0 : (c == 1 ? al * K.fv : al * (K.vc - v));
             }
-        wave_sync();
+        wave_lds_sync();
         if (live)
 #pragma unroll 1
             for (int e = g; e < 144; e += G) {
@@ -799,7 +793,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                 const double cq = div_plain(1.0, sqrt_ge1(tq * tq + 1.0));   // tq^2 + 1 in [1, 2]
                 const double c = rot ? cq : 1.0, sn = rot ? tq * cq : 0.0;
                 CS[g] = make_double2(c, sn);   // read back only at the p rows
-                wave_sync();
+                wave_lds_sync();
                 // columns p, q of every pair (own row of A; V's in the next round)
 #pragma unroll
                 for (int j = 0; j < 6; j++) {
@@ -815,7 +809,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                 const double dcol = my.x * dmine + mys * apq;
 #pragma unroll
                 for (int k = 0; k < 6; k++) RA2[g * (kRowStride / 2) + k] = make_double2(A[2 * k], A[2 * k + 1]);
-                wave_sync();
+                wave_lds_sync();
                 // the partner's column-updated row, kept for this round's row pass
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
@@ -831,13 +825,13 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                 dmine = my.x * dcol + mys * RAd[m * kRowStride + g];
                 apq = my.x * RAd[g * kRowStride + mn] + mys * RAd[m * kRowStride + mn];
                 dpart = __shfl(dmine, base + mn, 64);
-                wave_sync();   // this round's LDS reads are consumed before the next round's writes
+                wave_lds_sync();   // this round's LDS reads are consumed before the next round's writes
             }
         }
         if (sweep == 50) row_pass(10);   // (a break at the convergence test has applied it)
         apply_v(10);   // the last round of the last sweep
     }
-    wave_sync();
+    wave_lds_sync();
     if (live) {
 #pragma unroll
         for (int e = 0; e < 12; e++)   // static indices only: a run-time index would put A in scratch
@@ -855,7 +849,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
         uint4 oc = blk_off[gg];
         const uint32_t ij = kBlkTab.ij[gg], up0 = kBlkTab.up0[gg];
         const int bI = (int)(ij & 255u), bJ = (int)(ij >> 8);
-        wave_sync();   // M^T M in the LDS copy
+        wave_lds_sync();   // M^T M in the LDS copy
         if (live && ok0) {
             double x[4], y[4];
             // V's update of a round runs at the start of the next one, between the issue of that round's block
@@ -908,7 +902,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                     const double cq = div_plain(1.0, sqrt_ge1(tq * tq + 1.0));   // tq^2 + 1 in [1, 2]
                     const double c = rot ? cq : 1.0, sn = rot ? tq * cq : 0.0;
                     if (dg) CS[bI] = make_double2(c, sn);
-                    wave_sync();
+                    wave_lds_sync();
                     const double2 cI = CS[bI], cJ = CS[bJ];
 #pragma unroll
                     for (int j = 0; j < 6; j++) cvp[j] = CS[j];
@@ -929,22 +923,22 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                         st(o.z & 0xffffu, Y0); st(o.z >> 16, Y1); st(o.w & 0xffffu, Y2); st(o.w >> 16, Y3);
                     }
                     oc = on;
-                    wave_sync();   // the round's writes before the next round's reads (and CS reads before writes)
+                    wave_lds_sync();   // the round's writes before the next round's reads (and CS reads before writes)
                 }
             }
             apply_v(10);   // the last round of the last sweep (V rows g < 12; the other lanes' are unused)
         }
-        wave_sync();
+        wave_lds_sync();
         double dgv = 0.0;
         if (live && g < 12) dgv = reinterpret_cast<const double*>(Ab)[g * 13];
-        wave_sync();   // every diagonal read before V overwrites the LDS copy of A
+        wave_lds_sync();   // every diagonal read before V overwrites the LDS copy of A
         if (live && g < 12) {
             s.diag[g] = dgv;
 #pragma unroll
             for (int e = 0; e < 12; e++) s.V[g * 12 + e] = Vr[e];
         }
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(8);
     PNP_PROF_VAL(9, sweep);
 
@@ -968,14 +962,14 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
 #pragma unroll
         for (int k = 0; k < 4; k++) s.order[k] = id[k];
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(3);
     if (live)
         for (int e = g; e < 48; e += G) {
             const int k = e / 12, i = e % 12;
             s.ut[e] = s.V[i * 12 + s.order[k]];
         }
-    wave_sync();
+    wave_lds_sync();
     if (live && g < 6) {
         const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
         const int a = pa[g], b = pb[g];
@@ -998,7 +992,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
                      dz = s.cw[3 * a + 2] - s.cw[3 * b + 2];
         s.rho[g] = (dx * dx + dy * dy) + dz * dz;
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(4);
 
     // ---- beta candidates N = 1, 2, 3 on group lanes 0, 1, 2
@@ -1041,7 +1035,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
         gauss_newton(s.L, s.rho, b4);
         s.candE[g] = compute_R_and_t(s.pw, s.us, s.alphas, K, s.ut, b4, s.candR[g], s.candT[g]);
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(5);
     if (live && g == 0) {
         double best = INFINITY;
@@ -1054,7 +1048,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
             for (int i = 0; i < 3; i++) s.t[i] = s.candT[bi][i];
         }
     }
-    wave_sync();
+    wave_lds_sync();
     PNP_PROF(6);
     // ---- findInliers over every point of the problem
     const bool okm = s.ok != 0;
@@ -1079,7 +1073,7 @@ __device__ __forceinline__ void hyp_eval(HypLds& s, double2* CS, const uint4* __
         for (; i < count; i += G) cnt += reproj_err2(P3 + 3 * i, P2 + 2 * i, R, t, K) <= thr ? 1 : 0;
     }
     if (live) s.cnt[g] = cnt;
-    wave_sync();
+    wave_lds_sync();
     if (valid && g == 0) {
         int tot = 0;
         for (int k = 0; k < G; k++) tot += s.cnt[k];
@@ -1139,102 +1133,6 @@ __global__ __launch_bounds__(64, RGBD_HYP_EU) void k_pnp_hyp(const float* __rest
 }
 
 namespace {
-
-__device__ void sincos_poly(double x, double* s_out, double* c_out)
-{
-    const double PIO2_1 = 1.57079632673412561417e+00, PIO2_1T = 6.07710050650619224932e-11;
-    const double INV_PIO2 = 6.36619772367581382433e-01;
-    const double kd = floor(x * INV_PIO2 + 0.5);
-    const long k = (long)kd;
-    const double r = (x - kd * PIO2_1) - kd * PIO2_1T;
-    const double r2 = r * r;
-    double s = -1.0 / 121645100408832000.0;
-    s = s * r2 + 1.0 / 355687428096000.0;
-    s = s * r2 - 1.0 / 1307674368000.0;
-    s = s * r2 + 1.0 / 6227020800.0;
-    s = s * r2 - 1.0 / 39916800.0;
-    s = s * r2 + 1.0 / 362880.0;
-    s = s * r2 - 1.0 / 5040.0;
-    s = s * r2 + 1.0 / 120.0;
-    s = s * r2 - 1.0 / 6.0;
-    s = s * r2 + 1.0;
-    const double sr = s * r;
-    double c = -1.0 / 6402373705728000.0;
-    c = c * r2 + 1.0 / 20922789888000.0;
-    c = c * r2 - 1.0 / 87178291200.0;
-    c = c * r2 + 1.0 / 479001600.0;
-    c = c * r2 - 1.0 / 3628800.0;
-    c = c * r2 + 1.0 / 40320.0;
-    c = c * r2 - 1.0 / 720.0;
-    c = c * r2 + 1.0 / 24.0;
-    c = c * r2 - 0.5;
-    c = c * r2 + 1.0;
-    switch ((int)(k & 3)) {
-    case 0: *c_out = c; *s_out = sr; break;
-    case 1: *c_out = -sr; *s_out = c; break;
-    case 2: *c_out = -c; *s_out = -sr; break;
-    default: *c_out = sr; *s_out = -c; break;
-    }
-}
-
-__device__ void rodrigues_exp(const double w[3], double R[9])
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
-    const double th = sqrt(th2);
-    if (th < 1e-300) {
-        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        return;
-    }
-    double sn, c;
-    sincos_poly(th, &sn, &c);
-    const double k[3] = {w[0] / th, w[1] / th, w[2] / th};
-    const double c1 = 1.0 - c;
-    R[0] = c + c1 * k[0] * k[0];         R[1] = c1 * k[0] * k[1] - sn * k[2]; R[2] = c1 * k[0] * k[2] + sn * k[1];
-    R[3] = c1 * k[1] * k[0] + sn * k[2]; R[4] = c + c1 * k[1] * k[1];         R[5] = c1 * k[1] * k[2] - sn * k[0];
-    R[6] = c1 * k[2] * k[0] - sn * k[1]; R[7] = c1 * k[2] * k[1] + sn * k[0]; R[8] = c + c1 * k[2] * k[2];
-}
-
-__device__ __forceinline__ bool solve6(const double* H, const double* g, double x[6])
-{
-    double A[6][7];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-#pragma unroll
-        for (int j = 0; j < 6; j++) A[i][j] = H[i * 6 + j];
-        A[i][6] = -g[i];
-    }
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        int p = k;
-        double ap = fabs(A[k][k]);
-#pragma unroll
-        for (int i = k + 1; i < 6; i++)
-            if (fabs(A[i][k]) > ap) { p = i; ap = fabs(A[i][k]); }
-        // row swap k <-> p with static indices (p is run-time)
-#pragma unroll
-        for (int i = k + 1; i < 6; i++)
-            if (i == p)
-#pragma unroll
-                for (int j = 0; j < 7; j++) { const double tt = A[k][j]; A[k][j] = A[i][j]; A[i][j] = tt; }
-        if (A[k][k] == 0.0) ok = false;
-#pragma unroll
-        for (int i = k + 1; i < 6; i++) {
-            const double f = A[i][k] / A[k][k];
-#pragma unroll
-            for (int j = k; j < 7; j++) A[i][j] -= f * A[k][j];
-        }
-    }
-    if (!ok) return false;
-#pragma unroll
-    for (int k = 5; k >= 0; k--) {
-        double sacc = A[k][6];
-#pragma unroll
-        for (int j = k + 1; j < 6; j++) sacc -= A[k][j] * x[j];
-        x[k] = sacc / A[k][k];
-    }
-    return true;
-}
 
 // 21 upper-triangle entries of J^T J and 6 of J^T r for one correspondence (left SE(3) increment)
 __device__ __forceinline__ void gn_terms(const float* P, const float* uv, const double* R, const double* t,

@@ -23,6 +23,7 @@
 #include "launch.h"
 #include "ransac_dev.h"
 #include "svd3_dev.h"
+#include "wave_dev.h"
 
 #ifdef RGBD_PNP_PROFILE
 // lane 0's first hypothesis block of every k_ransac_hyp_lanes launch: wall-clock (10 ns) per refinement stage,
@@ -141,12 +142,7 @@ __device__ int rs_scan_excl(int* a, int n, int* wsum)
     int s = 0;
     for (int i = beg; i < end; i++) s += a[i];
     const int lane = tid & 63, w = tid >> 6;
-    int x = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
+    const int x = wave_incl_scan(s);
     if (lane == 63) wsum[w] = x;
     __syncthreads();
     int wpre = 0, total = 0;

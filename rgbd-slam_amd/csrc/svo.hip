@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "svo_dev.h"
+#include "wave_dev.h"
 
 namespace rgbd {
 
@@ -376,19 +377,6 @@ struct SelLds {
     int phase;       // block_scan2 buffer parity
     int first_false; // pair_swap: rank of the first left stopper that does not swap
 };
-
-// inclusive wave64 scan on DPP: row_shr 1/2/4/8 inside 16-lane rows, then row_bcast:15 / row_bcast:31
-// carry the row totals (out-of-row sources and masked rows contribute 0)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
 
 // exclusive block scan of (a, b) (each < 2^16 in total) in thread order: one packed DPP scan per wave,
 // the wave totals through LDS (double-buffered by the caller's phase bit, so one barrier per call)
