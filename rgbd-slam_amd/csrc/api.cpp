@@ -474,21 +474,12 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
     return RGBD_OK;
 }
 
-template <typename T>
-rgbd_status dalloc(rgbd_ctx* c, T** p, size_t count, const char* what)
-{
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    return check_hip(c, hipMalloc((void**)p, bytes), what);
-}
-
 // a later call that reads the extraction's outputs on another stream waits on this event
 // (order_after_extraction: rgbd_set_stream, and rgbd_track_lanes on the extracted frames)
 static rgbd_status mark_extracted(rgbd_ctx* c)
 {
-    rgbd_status s;
-    if (!c->extract_done &&
-        (s = check_hip(c, hipEventCreateWithFlags(&c->extract_done, hipEventDisableTiming), "extract event")))
-        return s;
+    rgbd_status s = check_hip(c, c->extract_done.ensure(), "extract event");
+    if (s) return s;
     if ((s = check_hip(c, hipEventRecord(c->extract_done, c->stream), "extract event record"))) return s;
     c->extract_stream = c->stream;
     return RGBD_OK;
@@ -556,10 +547,10 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
 #endif
     tk = timer_begin(c, "k_describe");
     RGBD_TRY(c, launch_describe(c->d_pyr, c->d_blur, c->d_selc, sel_count_elems(c->maxB, C.nlevels), C.nlevels, c->d_sel, c->d_cfg,
-                                C.kp_cap, c->d_count, c->d_kps, c->d_desc, B, st), "describe");
+                                C.kp_cap, c->out.count, c->out.kps, c->out.desc, B, st), "describe");
     timer_end(c, tk);
     tk = timer_begin(c, "k_undistort");
-    RGBD_TRY(c, launch_undistort(d_depth, c->d_count, c->d_cfg, C.kp_cap, c->d_kps, c->d_kun, c->d_xyz, B, st), "undistort");
+    RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, C.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
     timer_end(c, tk);
     c->last_B = B;
 #ifdef RGBD_PNP_PROFILE
@@ -573,7 +564,7 @@ rgbd_status read_frame(rgbd_ctx* c, int b, rgbd_keypoint* kps, rgbd_keypoint* ku
 {
     const int K = c->cfg.kp_cap;
     int cnt = 0;
-    rgbd_status s = check_hip(c, hipMemcpyAsync(&cnt, c->d_count + b, sizeof(int), hipMemcpyDeviceToHost, c->stream),
+    rgbd_status s = check_hip(c, hipMemcpyAsync(&cnt, c->out.count + b, sizeof(int), hipMemcpyDeviceToHost, c->stream),
                               "read count");
     if (s) return s;
     int errflag = 0;
@@ -586,10 +577,10 @@ rgbd_status read_frame(rgbd_ctx* c, int b, rgbd_keypoint* kps, rgbd_keypoint* ku
     if (cnt > cap) return fail(c, RGBD_ERR_CAPACITY, "output capacity smaller than keypoint count");
     if (cnt == 0) return RGBD_OK;
     const size_t o = (size_t)b * K;
-    if (kps && (s = check_hip(c, hipMemcpyAsync(kps, c->d_kps + o * 7, (size_t)cnt * 28, hipMemcpyDeviceToHost, c->stream), "read kps"))) return s;
-    if (kun && (s = check_hip(c, hipMemcpyAsync(kun, c->d_kun + o * 7, (size_t)cnt * 28, hipMemcpyDeviceToHost, c->stream), "read kun"))) return s;
-    if (desc && (s = check_hip(c, hipMemcpyAsync(desc, c->d_desc + o * 32, (size_t)cnt * 32, hipMemcpyDeviceToHost, c->stream), "read desc"))) return s;
-    if (xyz && (s = check_hip(c, hipMemcpyAsync(xyz, c->d_xyz + o * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost, c->stream), "read xyz"))) return s;
+    if (kps && (s = check_hip(c, hipMemcpyAsync(kps, c->out.kps + o * 7, (size_t)cnt * 28, hipMemcpyDeviceToHost, c->stream), "read kps"))) return s;
+    if (kun && (s = check_hip(c, hipMemcpyAsync(kun, c->out.kun + o * 7, (size_t)cnt * 28, hipMemcpyDeviceToHost, c->stream), "read kun"))) return s;
+    if (desc && (s = check_hip(c, hipMemcpyAsync(desc, c->out.desc + o * 32, (size_t)cnt * 32, hipMemcpyDeviceToHost, c->stream), "read desc"))) return s;
+    if (xyz && (s = check_hip(c, hipMemcpyAsync(xyz, c->out.xyz + o * 3, (size_t)cnt * 12, hipMemcpyDeviceToHost, c->stream), "read xyz"))) return s;
     return check_hip(c, hipStreamSynchronize(c->stream), "sync");
 }
 
@@ -628,32 +619,33 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
         *out = c;
         return fail(c, RGBD_ERR_CAPACITY, "max_batch x FAST cell lists exceed 4 GiB (use more contexts)");
     }
-    s = dalloc(c, &c->d_cfg, 1, "cfg");
-    if (!s) s = dalloc(c, &c->d_cells, C.n_cells, "cells");
-    if (!s) s = dalloc(c, &c->d_segs, c->segs.size(), "fast segments");
-    if (!s) s = dalloc(c, &c->d_rsx, g.rsx.size(), "rsx");
-    if (!s) s = dalloc(c, &c->d_qx, g.qx.size(), "resize quads");
-    if (!s) s = dalloc(c, &c->d_rsy, g.rsy.size(), "rsy");
-    if (!s) s = dalloc(c, &c->d_pyr, B * C.frame_pyr_bytes + 64, "pyramid");
-    if (!s) s = dalloc(c, &c->d_blur, B * C.frame_pyr_bytes + 64, "blurred pyramid");
-    if (!s) s = dalloc(c, &c->d_cellc, B * C.n_cells, "cell counts");
-    if (!s) s = dalloc(c, &c->d_slots, B * C.n_cells * C.cell_cap, "cell slots");
-    if (!s) s = dalloc(c, &c->d_keys, B * C.keys_per_frame, "keys");
-    if (!s) s = dalloc(c, &c->d_node, B * C.keys_per_frame, "node ids");
+    s = check_hip(c, c->d_cfg.alloc(1), "cfg");
+    if (!s) s = check_hip(c, c->d_cells.alloc(C.n_cells), "cells");
+    if (!s) s = check_hip(c, c->d_segs.alloc(c->segs.size()), "fast segments");
+    if (!s) s = check_hip(c, c->d_rsx.alloc(g.rsx.size()), "rsx");
+    if (!s) s = check_hip(c, c->d_qx.alloc(g.qx.size()), "resize quads");
+    if (!s) s = check_hip(c, c->d_rsy.alloc(g.rsy.size()), "rsy");
+    if (!s) s = check_hip(c, c->d_pyr.alloc(B * C.frame_pyr_bytes + 64), "pyramid");
+    if (!s) s = check_hip(c, c->d_blur.alloc(B * C.frame_pyr_bytes + 64), "blurred pyramid");
+    if (!s) s = check_hip(c, c->d_cellc.alloc(B * C.n_cells), "cell counts");
+    if (!s) s = check_hip(c, c->d_slots.alloc(B * C.n_cells * C.cell_cap), "cell slots");
+    if (!s) s = check_hip(c, c->d_keys.alloc(B * C.keys_per_frame), "keys");
+    if (!s) s = check_hip(c, c->d_node.alloc(B * C.keys_per_frame), "node ids");
     // + kMaxLevels of slack: k_describe reads kMaxLevels counts from any frame's row unconditionally
-    if (!s) s = dalloc(c, &c->d_selc, sel_count_elems((int)B, C.nlevels), "sel counts");
-    if (!s) s = dalloc(c, &c->d_sel, B * C.sel_per_frame, "sel");
-    if (!s) s = dalloc(c, &c->d_count, B, "counts");
-    if (!s) s = dalloc(c, &c->d_kps, B * C.kp_cap * 7, "kps");
-    if (!s) s = dalloc(c, &c->d_kun, B * C.kp_cap * 7, "kps_un");
-    if (!s) s = dalloc(c, &c->d_desc, B * C.kp_cap * 32, "desc");
-    if (!s) s = dalloc(c, &c->d_xyz, B * C.kp_cap * 3, "xyz");
-    if (!s) s = dalloc(c, &c->d_err, B, "err");   // one flag per frame
-    if (!s) s = dalloc(c, &c->d_in_bgr, (size_t)width * height * 3, "bgr staging");
-    if (!s) s = dalloc(c, &c->d_in_depth, (size_t)width * height, "depth staging");
-    if (!s) s = dalloc(c, &c->d_knn, B * C.kp_cap, "knn");
-    if (!s) s = dalloc(c, &c->d_pairs, 2 * B, "pairs");
+    if (!s) s = check_hip(c, c->d_selc.alloc(sel_count_elems((int)B, C.nlevels)), "sel counts");
+    if (!s) s = check_hip(c, c->d_sel.alloc(B * C.sel_per_frame), "sel");
+    if (!s) s = check_hip(c, c->own_out.count.alloc(B), "counts");
+    if (!s) s = check_hip(c, c->own_out.kps.alloc(B * C.kp_cap * 7), "kps");
+    if (!s) s = check_hip(c, c->own_out.kun.alloc(B * C.kp_cap * 7), "kps_un");
+    if (!s) s = check_hip(c, c->own_out.desc.alloc(B * C.kp_cap * 32), "desc");
+    if (!s) s = check_hip(c, c->own_out.xyz.alloc(B * C.kp_cap * 3), "xyz");
+    if (!s) s = check_hip(c, c->d_err.alloc(B), "err");   // one flag per frame
+    if (!s) s = check_hip(c, c->d_in_bgr.alloc((size_t)width * height * 3), "bgr staging");
+    if (!s) s = check_hip(c, c->d_in_depth.alloc((size_t)width * height), "depth staging");
+    if (!s) s = check_hip(c, c->own_out.knn.alloc(B * C.kp_cap), "knn");
+    if (!s) s = check_hip(c, c->d_pairs.alloc(2 * B), "pairs");
     if (s) { *out = c; return s; }
+    c->out = c->own_out.view();
     s = check_hip(c, hipMemcpy(c->d_cfg, &c->cfg, sizeof(ExtractCfg), hipMemcpyHostToDevice), "upload cfg");
     if (!s) s = check_hip(c, hipMemcpy(c->d_cells, c->cells.data(), c->cells.size() * sizeof(Cell), hipMemcpyHostToDevice), "upload cells");
     if (!s) s = check_hip(c, hipMemcpy(c->d_segs, c->segs.data(), c->segs.size() * sizeof(FastSeg), hipMemcpyHostToDevice), "upload segments");
@@ -696,24 +688,18 @@ void rgbd_destroy(rgbd_ctx* c)
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     if (c->solve_stream) (void)hipStreamSynchronize(c->solve_stream);
     if (c->match_stream) (void)hipStreamSynchronize(c->match_stream);
-    rgbd::pnp_free(c);   // first: restores the context's own output buffers (pipelined double buffering)
-    void* ptrs[] = {c->d_cfg, c->d_cells, c->d_segs, c->d_rsx, c->d_rsy, c->d_qx, c->d_pyr, c->d_blur, c->d_cellc, c->d_slots, c->d_keys,
-                    c->d_node, c->d_selc, c->d_sel, c->d_count, c->d_kps, c->d_kun, c->d_desc, c->d_xyz,
-                    c->d_err, c->d_in_bgr, c->d_in_depth, c->d_knn, c->d_pairs, c->d_mdesc, c->d_mcount,
-                    c->d_mknn};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    rgbd::pnp_free(c);
     rgbd::ransac_free(c);
     rgbd::gicp_free(c);
     rgbd::cloud_free(c);
     rgbd::svo_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    if (c->extract_done) (void)hipEventDestroy(c->extract_done);
-    for (hipStream_t* sp : {&c->solve_stream, &c->match_stream})   // serial: aliases of own_stream
-        if (*sp && *sp != c->own_stream) (void)hipStreamDestroy(*sp);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    const hipStream_t own = c->own_stream, solve = c->solve_stream, match = c->match_stream;
+    delete c;   // the context's buffers and its extraction event go here, before the streams
+    for (hipStream_t st : {solve, match})   // serial: aliases of own_stream
+        if (st && st != own) (void)hipStreamDestroy(st);
+    if (own) (void)hipStreamDestroy(own);
 }
 
 const char* rgbd_last_error(const rgbd_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -725,11 +711,11 @@ rgbd_status rgbd_debug_fast_rank16(rgbd_ctx* c, const uint8_t* flags, int32_t ro
     if (!c || rows < 1 || rows > 4096 || !flags || !slots || !counts) return RGBD_ERR_ARG;
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
-    uint8_t* d_f = nullptr;
-    uint32_t* d_s = nullptr;
+    DevBuf<uint8_t> d_f;
+    DevBuf<uint32_t> d_s;
     const size_t n = (size_t)rows * 64;
-    s = check_hip(c, hipMalloc((void**)&d_f, n), "rank flags");
-    if (!s) s = check_hip(c, hipMalloc((void**)&d_s, n * 4 + 64 * 4), "rank slots");
+    s = check_hip(c, d_f.alloc(n), "rank flags");
+    if (!s) s = check_hip(c, d_s.alloc(n + 64), "rank slots");
     if (!s) s = check_hip(c, hipMemcpyAsync(d_f, flags, n, hipMemcpyHostToDevice, c->stream), "rank in");
     if (!s) {
         s = check_hip(c, rgbd::launch_debug_rank16(d_f, rows, d_s, d_s + n, c->stream), "launch of k_debug_rank16");
@@ -737,8 +723,6 @@ rgbd_status rgbd_debug_fast_rank16(rgbd_ctx* c, const uint8_t* flags, int32_t ro
     if (!s) s = check_hip(c, hipMemcpyAsync(slots, d_s, n * 4, hipMemcpyDeviceToHost, c->stream), "rank out");
     if (!s) s = check_hip(c, hipMemcpyAsync(counts, d_s + n, 64 * 4, hipMemcpyDeviceToHost, c->stream), "rank counts");
     if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "rank sync");
-    if (d_f) (void)hipFree(d_f);
-    if (d_s) (void)hipFree(d_s);
     return s;
 }
 
@@ -807,11 +791,11 @@ rgbd_status rgbd_batch_frame(rgbd_ctx* c, int32_t b, rgbd_keypoint* kps, rgbd_ke
 rgbd_status rgbd_batch_outputs(rgbd_ctx* c, void** counts, void** kps, void** kun, void** desc, void** xyz)
 {
     if (!c) return RGBD_ERR_ARG;
-    if (counts) *counts = c->d_count;
-    if (kps) *kps = c->d_kps;
-    if (kun) *kun = c->d_kun;
-    if (desc) *desc = c->d_desc;
-    if (xyz) *xyz = c->d_xyz;
+    if (counts) *counts = c->out.count;
+    if (kps) *kps = c->out.kps;
+    if (kun) *kun = c->out.kun;
+    if (desc) *desc = c->out.desc;
+    if (xyz) *xyz = c->out.xyz;
     return RGBD_OK;
 }
 
@@ -888,22 +872,21 @@ rgbd_status rgbd_debug_selected(rgbd_ctx* c, int32_t b, int32_t level, int32_t* 
 }
 
 // ------------------------------------------------------------------ matching
-static rgbd_status ensure_mcap(rgbd_ctx* c, int need)
+// staging for query and train sets of `need` rows; *cap: the rows of each half of d_mdesc and of d_mknn that
+// both buffers hold, whichever of them a failed call left smaller
+static rgbd_status ensure_mcap(rgbd_ctx* c, int need, int* cap)
 {
-    if (need <= c->mcap) return RGBD_OK;
-    int cap = std::max(need, c->cfg.kp_cap);
-    if (c->d_mdesc) (void)hipFree(c->d_mdesc);
-    if (c->d_mcount) (void)hipFree(c->d_mcount);
-    if (c->d_mknn) (void)hipFree(c->d_mknn);
-    c->d_mdesc = nullptr; c->d_mcount = nullptr; c->d_mknn = nullptr;
-    rgbd_status s = dalloc(c, &c->d_mdesc, (size_t)2 * cap * 32, "match desc");
-    if (!s) s = dalloc(c, &c->d_mcount, 4, "match counts");
-    if (!s) s = dalloc(c, &c->d_mknn, (size_t)cap, "match knn");
-    if (!s) {
+    const size_t rows = (size_t)std::max(need, c->cfg.kp_cap);
+    const bool pairs = !c->d_mcount;
+    rgbd_status s = check_hip(c, c->d_mdesc.reserve(2 * rows * 32), "match desc");
+    if (!s) s = check_hip(c, c->d_mcount.reserve(4), "match counts");
+    if (!s) s = check_hip(c, c->d_mknn.reserve(rows), "match knn");
+    if (!s && pairs) {
         int pr[2] = {0, 1};
         s = check_hip(c, hipMemcpy(c->d_mcount + 2, pr, 8, hipMemcpyHostToDevice), "pairs");
     }
-    if (!s) c->mcap = cap;
+    if (s && pairs) c->d_mcount.release();   // the pairs are written once, with the allocation
+    *cap = (int)std::min(c->d_mdesc.capacity() / 64, c->d_mknn.capacity());
     return s;
 }
 
@@ -913,8 +896,8 @@ rgbd_status rgbd_knn2(rgbd_ctx* c, const uint8_t* dq, int32_t nq, const uint8_t*
     if (nq == 0) return RGBD_OK;
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
-    if ((s = ensure_mcap(c, std::max(nq, nt)))) return s;
-    const int cap = c->mcap;
+    int cap = 0;
+    if ((s = ensure_mcap(c, std::max(nq, nt), &cap))) return s;
     int counts[2] = {nq, nt};
     if ((s = check_hip(c, hipMemcpyAsync(c->d_mcount, counts, 8, hipMemcpyHostToDevice, c->stream), "counts"))) return s;
     if ((s = check_hip(c, hipMemcpyAsync(c->d_mdesc, dq, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream), "dq"))) return s;

@@ -15,22 +15,17 @@ namespace rgbd {
 
 struct CloudWS {
     int cap = 0, nkf = 0;
-    CloudPoint *d_pts = nullptr, *d_vox = nullptr, *d_out = nullptr;
-    float* d_dist = nullptr;
-    int *d_nvox = nullptr, *d_nout = nullptr, *d_frames = nullptr;
-    uint8_t* d_bgr = nullptr;   // single-frame staging (host-buffer entry point)
-    uint16_t* d_depth = nullptr;
-    float* d_depthf = nullptr;  // ... Frame::mImDepth (f32) for rgbd_keyframe_cloud_f32
+    DevBuf<CloudPoint> d_pts, d_vox, d_out;
+    DevBuf<float> d_dist;
+    DevBuf<int> d_nvox, d_nout, d_frames;
+    DevBuf<uint8_t> d_bgr;      // single-frame staging (host-buffer entry point)
+    DevBuf<uint16_t> d_depth;
+    DevBuf<float> d_depthf;     // ... Frame::mImDepth (f32) for rgbd_keyframe_cloud_f32
 };
 
 void cloud_free(rgbd_ctx* c)
 {
-    CloudWS* w = static_cast<CloudWS*>(c->cloud);
-    if (!w) return;
-    void* p[] = {w->d_pts, w->d_vox, w->d_out, w->d_dist, w->d_nvox, w->d_nout, w->d_frames, w->d_bgr, w->d_depth, w->d_depthf};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete w;
+    delete c->cloud;
     c->cloud = nullptr;
 }
 
@@ -64,28 +59,21 @@ rgbd_status cloud_cfg(rgbd_ctx* c, const rgbd_cloud_params* prm, CloudCfg* g)
     return RGBD_OK;
 }
 
-template <typename T>
-rgbd_status dgrow(rgbd_ctx* c, T** p, size_t n, const char* what)
-{
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    return check_hip(c, hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)), what);
-}
-
 rgbd_status ws_get(rgbd_ctx* c, int cap, int nkf, CloudWS** out)
 {
-    CloudWS* w = static_cast<CloudWS*>(c->cloud);
+    CloudWS* w = c->cloud;
     if (!w) c->cloud = w = new CloudWS();
     if (w->cap < cap || w->nkf < nkf) {
         const int nk = std::max(nkf, w->nkf);
         const size_t np = (size_t)cap * nk;
-        rgbd_status s = dgrow(c, &w->d_pts, np, "cloud pts");
-        if (!s) s = dgrow(c, &w->d_vox, np, "cloud vox");
-        if (!s) s = dgrow(c, &w->d_out, np, "cloud out");
-        if (!s) s = dgrow(c, &w->d_dist, np, "cloud dist");
-        if (!s) s = dgrow(c, &w->d_nvox, (size_t)nk, "cloud nvox");
-        if (!s) s = dgrow(c, &w->d_nout, (size_t)nk, "cloud nout");
-        if (!s) s = dgrow(c, &w->d_frames, (size_t)nk, "cloud frames");
+        w->cap = 0;   // no capacity until all seven buffers are there
+        rgbd_status s = check_hip(c, w->d_pts.alloc(np), "cloud pts");
+        if (!s) s = check_hip(c, w->d_vox.alloc(np), "cloud vox");
+        if (!s) s = check_hip(c, w->d_out.alloc(np), "cloud out");
+        if (!s) s = check_hip(c, w->d_dist.alloc(np), "cloud dist");
+        if (!s) s = check_hip(c, w->d_nvox.alloc((size_t)nk), "cloud nvox");
+        if (!s) s = check_hip(c, w->d_nout.alloc((size_t)nk), "cloud nout");
+        if (!s) s = check_hip(c, w->d_frames.alloc((size_t)nk), "cloud frames");
         if (s) return s;
         w->cap = cap;
         w->nkf = nk;
@@ -139,9 +127,9 @@ rgbd_status cloud_host_frame(rgbd_ctx* c, const uint8_t* bgr, const uint16_t* de
     CloudWS* w = nullptr;
     if ((s = ws_get(c, g.cap, 1, &w))) return s;
     const size_t px = (size_t)c->W * c->H;
-    if (!w->d_bgr) s = check_hip(c, hipMalloc((void**)&w->d_bgr, px * 3), "cloud bgr");
-    if (!s && depth && !w->d_depth) s = check_hip(c, hipMalloc((void**)&w->d_depth, px * 2), "cloud depth");
-    if (!s && depthf && !w->d_depthf) s = check_hip(c, hipMalloc((void**)&w->d_depthf, px * 4), "cloud depth f32");
+    if (!w->d_bgr) s = check_hip(c, w->d_bgr.alloc(px * 3), "cloud bgr");
+    if (!s && depth && !w->d_depth) s = check_hip(c, w->d_depth.alloc(px), "cloud depth");
+    if (!s && depthf && !w->d_depthf) s = check_hip(c, w->d_depthf.alloc(px), "cloud depth f32");
     if (!s) s = check_hip(c, hipMemcpyAsync(w->d_bgr, bgr, px * 3, hipMemcpyHostToDevice, c->stream), "cloud bgr up");
     if (!s && depth)
         s = check_hip(c, hipMemcpyAsync(w->d_depth, depth, px * 2, hipMemcpyHostToDevice, c->stream), "cloud depth up");
@@ -149,7 +137,7 @@ rgbd_status cloud_host_frame(rgbd_ctx* c, const uint8_t* bgr, const uint16_t* de
         s = check_hip(c, hipMemcpyAsync(w->d_depthf, depthf, px * 4, hipMemcpyHostToDevice, c->stream), "cloud depth up");
     if (s) return s;
     const int32_t f0 = 0;
-    return run_cloud(c, w->d_bgr, depth ? w->d_depth : nullptr, depthf ? w->d_depthf : nullptr, &f0, 1, prm, out, cap, n);
+    return run_cloud(c, w->d_bgr, depth ? w->d_depth.get() : nullptr, depthf ? w->d_depthf.get() : nullptr, &f0, 1, prm, out, cap, n);
 }
 
 }  // namespace

@@ -7,7 +7,29 @@
 #include <vector>
 
 #include "../../include/rgbd_hip.h"
+#include "devmem.h"
 #include "rgbd_internal.h"
+
+namespace rgbd {
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS;
+// the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
+struct OutSet {
+    int* count = nullptr;
+    float* kps = nullptr;
+    float* kun = nullptr;
+    uint8_t* desc = nullptr;
+    float* xyz = nullptr;
+    int4* knn = nullptr;
+};
+struct OutBufs {   // one owned set
+    DevBuf<int> count;
+    DevBuf<float> kps, kun;
+    DevBuf<uint8_t> desc;
+    DevBuf<float> xyz;
+    DevBuf<int4> knn;
+    OutSet view() const { return OutSet{count, kps, kun, desc, xyz, knn}; }
+};
+}  // namespace rgbd
 
 struct rgbd_ctx {
     int device = 0;
@@ -28,48 +50,44 @@ struct rgbd_ctx {
                                          // (kernels never overlap: attributable PMC counters)
 
     // device workspace
-    rgbd::ExtractCfg* d_cfg = nullptr;
-    rgbd::Cell* d_cells = nullptr;
-    rgbd::FastSeg* d_segs = nullptr;
-    rgbd::ResizeX* d_rsx = nullptr;
-    rgbd::ResizeY* d_rsy = nullptr;
-    rgbd::QuadX* d_qx = nullptr;
-    uint8_t* d_pyr = nullptr;
-    uint8_t* d_blur = nullptr;           // blurred pyramid, same layout as d_pyr
-    int* d_cellc = nullptr;
-    uint32_t* d_slots = nullptr;
-    uint32_t* d_keys = nullptr;
-    uint16_t* d_node = nullptr;
-    int* d_selc = nullptr;
-    uint32_t* d_sel = nullptr;
-    int* d_count = nullptr;
-    float* d_kps = nullptr;
-    float* d_kun = nullptr;
-    uint8_t* d_desc = nullptr;
-    float* d_xyz = nullptr;
-    int* d_err = nullptr;
-    uint8_t* d_in_bgr = nullptr;         // single-frame staging (host-buffer entry points)
-    uint16_t* d_in_depth = nullptr;
-    int4* d_knn = nullptr;               // [maxB][kp_cap]
-    int* d_pairs = nullptr;              // qf[maxB], tf[maxB]
+    rgbd::DevBuf<rgbd::ExtractCfg> d_cfg;
+    rgbd::DevBuf<rgbd::Cell> d_cells;
+    rgbd::DevBuf<rgbd::FastSeg> d_segs;
+    rgbd::DevBuf<rgbd::ResizeX> d_rsx;
+    rgbd::DevBuf<rgbd::ResizeY> d_rsy;
+    rgbd::DevBuf<rgbd::QuadX> d_qx;
+    rgbd::DevBuf<uint8_t> d_pyr;
+    rgbd::DevBuf<uint8_t> d_blur;              // blurred pyramid, same layout as d_pyr
+    rgbd::DevBuf<int> d_cellc;
+    rgbd::DevBuf<uint32_t> d_slots;
+    rgbd::DevBuf<uint32_t> d_keys;
+    rgbd::DevBuf<uint16_t> d_node;
+    rgbd::DevBuf<int> d_selc;
+    rgbd::DevBuf<uint32_t> d_sel;
+    rgbd::OutBufs own_out;               // the context's own output set; knn: [maxB][kp_cap]
+    rgbd::OutSet out{};                  // the set the kernels read and write: own_out unless a pipelined
+                                         // submission selected the second one (pnp_host.cpp)
+    rgbd::DevBuf<int> d_err;
+    rgbd::DevBuf<uint8_t> d_in_bgr;            // single-frame staging (host-buffer entry points)
+    rgbd::DevBuf<uint16_t> d_in_depth;
+    rgbd::DevBuf<int> d_pairs;                 // qf[maxB], tf[maxB]
     // host-array knn staging
-    uint8_t* d_mdesc = nullptr;
-    int* d_mcount = nullptr;
-    int4* d_mknn = nullptr;
-    int mcap = 0;
+    rgbd::DevBuf<uint8_t> d_mdesc;
+    rgbd::DevBuf<int> d_mcount;
+    rgbd::DevBuf<int4> d_mknn;
     int last_B = 0;
-    hipEvent_t extract_done = nullptr;   // recorded after every extraction on the stream it ran on
+    rgbd::Event extract_done;            // recorded after every extraction on the stream it ran on
     hipStream_t extract_stream = nullptr;
 
-    // ransac workspace (solver.cpp), PnPRansac workspace (pnp_host.cpp)
-    void* ransac = nullptr;
-    void* pnp = nullptr;
-    void* pnp_pipe = nullptr;            // two PnPRansac workspaces of the submit / collect tracking API
+    // workspaces, each owned and freed by the file that defines it (*_free below)
+    rgbd::RansacWS* ransac = nullptr;    // solver.cpp
+    rgbd::PnpWS* pnp = nullptr;          // PnPRansac (pnp_host.cpp)
+    rgbd::PnpPipe* pnp_pipe = nullptr;   // the PnPRansac workspaces of the submit / collect tracking API
     int pnp_chunk = 0, pnp_chunk2 = 0;   // PnPRansac device chunks, adapted per solve (pnp_host.cpp)
-    void* gicp = nullptr;                // GICP workspace (gicp_host.cpp)
-    void* lanes = nullptr;               // device-resident RansacSE3 tracking chain workspace (lanes_host.cpp)
-    void* cloud = nullptr;               // keyframe cloud workspace (cloud_host.cpp)
-    void* svo = nullptr;                 // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
+    rgbd::GicpWS* gicp = nullptr;        // gicp_host.cpp
+    rgbd::LaneWS* lanes = nullptr;       // device-resident RansacSE3 tracking chain (lanes_host.cpp)
+    rgbd::CloudWS* cloud = nullptr;      // keyframe cloud (cloud_host.cpp)
+    rgbd::SvoWS* svo = nullptr;          // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
     rgbd_gicp_params track_gicp{10, 20, 0.07, 1e-9, 2e-3, 1e-3, 4, 1};
 
     // timing

@@ -16,41 +16,33 @@ using namespace rgbd;
 namespace rgbd {
 
 struct GicpWS {
-    float* d_pts = nullptr;      // src [kGicpMaxM][3] | tgt [kGicpMaxM][3] | guess[16]
-    double* d_cov = nullptr;     // [2][kGicpMaxM][9]
-    double* d_M = nullptr;       // [kGicpMaxM][9] Mahalanobis matrices of one outer iteration
-    GicpOut* d_out = nullptr;
-    float* h_pts = nullptr;      // pinned mirror of d_pts
-    GicpOut* h_out = nullptr;
+    DevBuf<float> d_pts;         // src [kGicpMaxM][3] | tgt [kGicpMaxM][3] | guess[16]
+    DevBuf<double> d_cov;        // [2][kGicpMaxM][9]
+    DevBuf<double> d_M;          // [kGicpMaxM][9] Mahalanobis matrices of one outer iteration
+    DevBuf<GicpOut> d_out;
+    PinnedBuf<float> h_pts;      // pinned mirror of d_pts
+    PinnedBuf<GicpOut> h_out;
 };
 
 void gicp_free(rgbd_ctx* c)
 {
-    GicpWS* w = static_cast<GicpWS*>(c->gicp);
-    if (!w) return;
-    if (w->d_pts) (void)hipFree(w->d_pts);
-    if (w->d_cov) (void)hipFree(w->d_cov);
-    if (w->d_M) (void)hipFree(w->d_M);
-    if (w->d_out) (void)hipFree(w->d_out);
-    if (w->h_pts) (void)hipHostFree(w->h_pts);
-    if (w->h_out) (void)hipHostFree(w->h_out);
-    delete w;
+    delete c->gicp;
     c->gicp = nullptr;
 }
 
 static rgbd_status gicp_ws(rgbd_ctx* c, GicpWS** out)
 {
-    GicpWS* w = static_cast<GicpWS*>(c->gicp);
+    GicpWS* w = c->gicp;
     if (!w) {
         w = new GicpWS();
         c->gicp = w;
-        const size_t pts = ((size_t)2 * kGicpMaxM * 3 + 16) * sizeof(float);
-        rgbd_status s = check_hip(c, hipMalloc((void**)&w->d_pts, pts), "gicp pts");
-        if (!s) s = check_hip(c, hipMalloc((void**)&w->d_cov, (size_t)2 * kGicpMaxM * 9 * sizeof(double)), "gicp cov");
-        if (!s) s = check_hip(c, hipMalloc((void**)&w->d_M, (size_t)kGicpMaxM * 9 * sizeof(double)), "gicp M");
-        if (!s) s = check_hip(c, hipMalloc((void**)&w->d_out, sizeof(GicpOut)), "gicp out");
-        if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_pts, pts, hipHostMallocDefault), "gicp pinned pts");
-        if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_out, sizeof(GicpOut), hipHostMallocDefault), "gicp pinned out");
+        const size_t pts = (size_t)2 * kGicpMaxM * 3 + 16;
+        rgbd_status s = check_hip(c, w->d_pts.alloc(pts), "gicp pts");
+        if (!s) s = check_hip(c, w->d_cov.alloc((size_t)2 * kGicpMaxM * 9), "gicp cov");
+        if (!s) s = check_hip(c, w->d_M.alloc((size_t)kGicpMaxM * 9), "gicp M");
+        if (!s) s = check_hip(c, w->d_out.alloc(1), "gicp out");
+        if (!s) s = check_hip(c, w->h_pts.alloc(pts), "gicp pinned pts");
+        if (!s) s = check_hip(c, w->h_out.alloc(1), "gicp pinned out");
         if (s) {
             gicp_free(c);
             return s;
@@ -94,7 +86,7 @@ rgbd_status gicp_align(rgbd_ctx* c, int M, const float* guess, const rgbd_gicp_p
     s = check_hip(c, hipMemcpyAsync(w->h_out, w->d_out, sizeof(GicpOut), hipMemcpyDeviceToHost, st), "gicp out");
     if (!s) s = check_hip(c, hipStreamSynchronize(st), "sync");
     if (s) return s;
-    *res = *w->h_out;
+    *res = *w->h_out.get();
     return RGBD_OK;
 }
 

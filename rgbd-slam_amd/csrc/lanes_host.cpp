@@ -42,63 +42,48 @@ constexpr int kLaneWindow = RGBD_LANE_WINDOW;
 struct LaneWS {
     int capL = 0, capB = 0, K = 0, H = 0, SS = 0, Mcap = 0, MWcap = 0, GM = 0;
     bool gicp = false;          // GICP problem slots allocated (only for calls that run GICP)
-    LaneBufs d{};
-    std::vector<void*> owned;
-    LaneCtl* h_ctl = nullptr;   // pinned
-    PairOut* h_out = nullptr;   // pinned
-    hipEvent_t ev_window[2] = {nullptr, nullptr};   // round markers bounding the rounds in flight
-    int* d_pairs = nullptr;     // consecutive pairs (p, p + 1): [capB = maxB] query | [capB] train, then the
+    LaneBufs d{};               // what the kernels get: the raw pointers of `own`, filled as it is allocated
+    struct {
+        DevBuf<LaneCtl> ctl;
+        DevBuf<PairOut> out;
+        DevBuf<uint8_t> flags;
+        DevBuf<int4> knn_r;
+        DevBuf<int> rq, rt, samples, scount, snap, gn, plist, ppre, pcount, done;
+        DevBuf<int2> mt;
+        DevBuf<float> pts, gsrc, gtgt, gguess;
+        DevBuf<HypOut> hyp;
+        DevBuf<uint32_t> masks;
+        DevBuf<double> gcov, gM;
+        DevBuf<GicpOut> gout;
+    } own;
+    PinnedBuf<LaneCtl> h_ctl;
+    PinnedBuf<PairOut> h_out;
+    Event ev_window[2];         // round markers bounding the rounds in flight
+    DevBuf<int> d_pairs;        // consecutive pairs (p, p + 1): [capB = maxB] query | [capB] train, then the
                                 // pairs (p, p + 2) the same way
-    int4* d_knn_skip = nullptr; // [capB][K] knn-2 rows of the pairs (p, p + 2)
+    DevBuf<int4> d_knn_skip;    // [capB][K] knn-2 rows of the pairs (p, p + 2)
 };
-
-static void ws_free(LaneWS* w)
-{
-    for (void* p : w->owned) (void)hipFree(p);
-    w->owned.clear();
-    if (w->h_ctl) (void)hipHostFree(w->h_ctl);
-    if (w->h_out) (void)hipHostFree(w->h_out);
-    for (hipEvent_t& e : w->ev_window) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    w->h_ctl = nullptr;
-    w->h_out = nullptr;
-    w->d = LaneBufs{};
-    w->d_pairs = nullptr;
-    w->d_knn_skip = nullptr;
-}
 
 void lanes_free(rgbd_ctx* c)
 {
-    LaneWS* w = static_cast<LaneWS*>(c->lanes);
-    if (!w) return;
-    ws_free(w);
-    delete w;
+    delete c->lanes;
     c->lanes = nullptr;
-}
-
-template <typename T>
-static rgbd_status dal(rgbd_ctx* c, LaneWS* w, T** p, size_t n, const char* what)
-{
-    rgbd_status s = check_hip(c, hipMalloc((void**)p, std::max<size_t>(n * sizeof(T), 16)), what);
-    if (!s) w->owned.push_back((void*)*p);
-    return s;
 }
 
 static rgbd_status lanes_ws(rgbd_ctx* c, int L, int H, int SS, bool gicp, LaneWS** out)
 {
-    LaneWS* w = static_cast<LaneWS*>(c->lanes);
-    if (!w) {
-        w = new LaneWS();
-        c->lanes = w;
-    }
+    LaneWS* w = c->lanes;   // exists only with every buffer allocated
     const int K = c->cfg.kp_cap, B = c->maxB;
-    if (w->d.ctl && L <= w->capL && H <= w->H && SS <= w->SS && (!gicp || w->gicp)) {
+    if (w && L <= w->capL && H <= w->H && SS <= w->SS && (!gicp || w->gicp)) {
         *out = w;
         return RGBD_OK;
     }
-    ws_free(w);
+    // a fresh workspace no smaller than the old one, which is released first
+    LaneWS* const old = w;
+    w = new LaneWS();
+    if (old) w->capL = old->capL, w->H = old->H, w->SS = old->SS, w->gicp = old->gicp;
+    lanes_free(c);
+    c->lanes = w;
     w->capL = std::max(L, w->capL);
     w->capB = B;
     w->K = K;
@@ -110,37 +95,42 @@ static rgbd_status lanes_ws(rgbd_ctx* c, int L, int H, int SS, bool gicp, LaneWS
     w->gicp = gicp || w->gicp;
     const size_t Lc = (size_t)w->capL, Hc = (size_t)w->H;
     LaneBufs& d = w->d;
-    rgbd_status s = dal(c, w, &d.ctl, Lc, "lane ctl");
-    if (!s) s = dal(c, w, &d.out, (size_t)B, "lane pair out");
-    if (!s) s = dal(c, w, &d.flags, ((size_t)B + Lc) * K, "lane flags");
-    if (!s) s = dal(c, w, &d.knn_r, Lc * K, "lane knn rows");
-    if (!s) s = dal(c, w, &d.rq, Lc, "lane rq");
-    if (!s) s = dal(c, w, &d.rt, Lc, "lane rt");
-    if (!s) s = dal(c, w, &d.mt, Lc * w->Mcap, "lane matches");
-    if (!s) s = dal(c, w, &d.pts, Lc * w->Mcap * 6, "lane points");
-    if (!s) s = dal(c, w, &d.samples, Lc * Hc * w->SS, "lane samples");
-    if (!s) s = dal(c, w, &d.scount, Lc * Hc, "lane sample counts");
-    if (!s) s = dal(c, w, &d.snap, Lc * Hc, "lane rand counts");
-    if (!s) s = dal(c, w, &d.hyp, Lc * (Hc + 1), "lane hypotheses");
-    if (!s) s = dal(c, w, &d.masks, Lc * (Hc + 1) * w->MWcap, "lane masks");
+    auto dal = [&](auto& buf, auto*& view, size_t n, const char* what) {
+        const rgbd_status e = check_hip(c, buf.alloc(n), what);
+        view = buf;
+        return e;
+    };
+    rgbd_status s = dal(w->own.ctl, d.ctl, Lc, "lane ctl");
+    if (!s) s = dal(w->own.out, d.out, (size_t)B, "lane pair out");
+    if (!s) s = dal(w->own.flags, d.flags, ((size_t)B + Lc) * K, "lane flags");
+    if (!s) s = dal(w->own.knn_r, d.knn_r, Lc * K, "lane knn rows");
+    if (!s) s = dal(w->own.rq, d.rq, Lc, "lane rq");
+    if (!s) s = dal(w->own.rt, d.rt, Lc, "lane rt");
+    if (!s) s = dal(w->own.mt, d.mt, Lc * w->Mcap, "lane matches");
+    if (!s) s = dal(w->own.pts, d.pts, Lc * w->Mcap * 6, "lane points");
+    if (!s) s = dal(w->own.samples, d.samples, Lc * Hc * w->SS, "lane samples");
+    if (!s) s = dal(w->own.scount, d.scount, Lc * Hc, "lane sample counts");
+    if (!s) s = dal(w->own.snap, d.snap, Lc * Hc, "lane rand counts");
+    if (!s) s = dal(w->own.hyp, d.hyp, Lc * (Hc + 1), "lane hypotheses");
+    if (!s) s = dal(w->own.masks, d.masks, Lc * (Hc + 1) * w->MWcap, "lane masks");
     // GICP problem slots, one per pair (~0.5 GB at max_batch 1024): only when a call runs GICP
     const size_t Bs = (size_t)B, GM = w->gicp ? (size_t)w->GM : 0;
-    if (!s) s = dal(c, w, &d.gn, Bs, "gicp n");
-    if (!s) s = dal(c, w, &d.gsrc, Bs * GM * 3, "gicp src");
-    if (!s) s = dal(c, w, &d.gtgt, Bs * GM * 3, "gicp tgt");
-    if (!s) s = dal(c, w, &d.gguess, Bs * 16, "gicp guess");
-    if (!s) s = dal(c, w, &d.gcov, Bs * 2 * GM * 9, "gicp cov");
-    if (!s) s = dal(c, w, &d.gM, Bs * GM * 9, "gicp M");
-    if (!s) s = dal(c, w, &d.gout, Bs, "gicp out");
-    if (!s) s = dal(c, w, &d.plist, Bs, "gicp list");
-    if (!s) s = dal(c, w, &d.ppre, Bs, "gicp prefix");
-    if (!s) s = dal(c, w, &d.pcount, 2, "gicp count");
-    if (!s) s = dal(c, w, &d.done, Lc, "lane done counts");
+    if (!s) s = dal(w->own.gn, d.gn, Bs, "gicp n");
+    if (!s) s = dal(w->own.gsrc, d.gsrc, Bs * GM * 3, "gicp src");
+    if (!s) s = dal(w->own.gtgt, d.gtgt, Bs * GM * 3, "gicp tgt");
+    if (!s) s = dal(w->own.gguess, d.gguess, Bs * 16, "gicp guess");
+    if (!s) s = dal(w->own.gcov, d.gcov, Bs * 2 * GM * 9, "gicp cov");
+    if (!s) s = dal(w->own.gM, d.gM, Bs * GM * 9, "gicp M");
+    if (!s) s = dal(w->own.gout, d.gout, Bs, "gicp out");
+    if (!s) s = dal(w->own.plist, d.plist, Bs, "gicp list");
+    if (!s) s = dal(w->own.ppre, d.ppre, Bs, "gicp prefix");
+    if (!s) s = dal(w->own.pcount, d.pcount, 2, "gicp count");
+    if (!s) s = dal(w->own.done, d.done, Lc, "lane done counts");
     if (!s) s = check_hip(c, hipMemset(d.done, 0, Lc * sizeof(int)), "lane done clear");
-    if (!s) s = dal(c, w, &w->d_pairs, 4 * (size_t)B, "lane pairs");
-    if (!s) s = dal(c, w, &w->d_knn_skip, (size_t)B * K, "lane second-reference rows");
-    if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_ctl, Lc * sizeof(LaneCtl), hipHostMallocDefault), "lane ctl pinned");
-    if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_out, (size_t)B * sizeof(PairOut), hipHostMallocDefault), "lane out pinned");
+    if (!s) s = check_hip(c, w->d_pairs.alloc(4 * (size_t)B), "lane pairs");
+    if (!s) s = check_hip(c, w->d_knn_skip.alloc((size_t)B * K), "lane second-reference rows");
+    if (!s) s = check_hip(c, w->h_ctl.alloc(Lc), "lane ctl pinned");
+    if (!s) s = check_hip(c, w->h_out.alloc((size_t)B), "lane out pinned");
     if (!s) {
         std::vector<int> pairs(4 * (size_t)B, 0);
         for (int p = 0; p + 1 < B; p++) {
@@ -154,14 +144,14 @@ static rgbd_status lanes_ws(rgbd_ctx* c, int L, int H, int SS, bool gicp, LaneWS
         s = check_hip(c, hipMemcpy(w->d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice), "lane pairs");
     }
     if (s) {
-        ws_free(w);
+        lanes_free(c);
         return s;
     }
     *out = w;
     return RGBD_OK;
 }
 
-static void raster_consts(double* rcx, double* rcy)
+void raster_consts(double* rcx, double* rcy)
 {
     const double cam_angle_x = 58.0 / 180.0 * M_PI;   // Solver/SolverSE3.cpp:218-225
     const double cam_angle_y = 45.0 / 180.0 * M_PI;
@@ -187,7 +177,7 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
     // knn-2 rows of every consecutive pair (query = frame p, train = frame p + 1)
     if (B > 1) {
         const int tk = timer_begin(c, "k_knn2");
-        RGBD_TRY(c, launch_knn2(c->d_desc, c->d_count, w->d_pairs, w->d_pairs + w->capB, K, K, c->d_knn, B - 1, st), "knn2");
+        RGBD_TRY(c, launch_knn2(c->out.desc, c->out.count, w->d_pairs, w->d_pairs + w->capB, K, K, c->out.knn, B - 1, st), "knn2");
         timer_end(c, tk);
     }
     // few lanes: the second references' rows (p -> p + 2) of every frame in one launch here, instead of a
@@ -196,14 +186,14 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
     const bool skip_rows = L <= kLaneFuseMax;
     if (skip_rows && B > 2) {
         const int tk = timer_begin(c, "k_knn2");
-        RGBD_TRY(c, launch_knn2(c->d_desc, c->d_count, w->d_pairs + 2 * (size_t)w->capB, w->d_pairs + 3 * (size_t)w->capB, K, K,
+        RGBD_TRY(c, launch_knn2(c->out.desc, c->out.count, w->d_pairs + 2 * (size_t)w->capB, w->d_pairs + 3 * (size_t)w->capB, K, K,
                                 w->d_knn_skip, B - 2, st), "knn2 skip");
         timer_end(c, tk);
     }
     LaneBufs lb = w->d;
-    lb.counts = c->d_count;
-    lb.xyz = c->d_xyz;
-    lb.knn = c->d_knn;
+    lb.counts = c->out.count;
+    lb.xyz = c->out.xyz;
+    lb.knn = c->out.knn;
     lb.knn_skip = w->d_knn_skip;
     // every frame starts with clear outlier flags; a continuing chunk's first two frames carry theirs
     s = check_hip(c, hipMemsetAsync(lb.flags, 0, ((size_t)B + L) * K, st), "lane flags clear");
@@ -265,8 +255,8 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
     s = check_hip(c, hipMemsetAsync(lb.rq, 0xff, (size_t)L * sizeof(int), st), "second references clear");
     if (s) return s;
     bool any_retry = false;   // no second-reference rows are due before the first round
-    for (hipEvent_t& e : w->ev_window)
-        if (!e && (s = check_hip(c, hipEventCreateWithFlags(&e, hipEventDisableTiming), "lane window event"))) return s;
+    for (Event& e : w->ev_window)
+        if ((s = check_hip(c, e.ensure(), "lane window event"))) return s;
     bool marked[2] = {false, false};
     int enqueued = 0;   // rounds enqueued by this call
     for (int left = rounds; left > 0;) {
@@ -280,7 +270,7 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
             enqueued++;
             if (!skip_rows && (any_retry || r > 0)) {
                 const int tk = timer_begin(c, "k_knn2");
-                RGBD_TRY(c, launch_knn2(c->d_desc, c->d_count, lb.rq, lb.rt, K, K, lb.knn_r, L, st), "knn2");
+                RGBD_TRY(c, launch_knn2(c->out.desc, c->out.count, lb.rq, lb.rt, K, K, lb.knn_r, L, st), "knn2");
                 timer_end(c, tk);
             }
             int tk = timer_begin(c, "k_lane_match");
@@ -342,25 +332,22 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
         stickies[l].cov = k.cov;
         stickies[l].set = k.cov_set;
     }
-    out.assign(w->h_out, w->h_out + B);
+    out.assign(w->h_out.get(), w->h_out + B);
     return RGBD_OK;
 }
 
 rgbd_status lanes_sort_test(rgbd_ctx* c, const float* dist, int n, int depth_limit, int* order)
 {
-    float* d_dist = nullptr;
-    int* d_order = nullptr;
-    rgbd_status s = check_hip(c, hipMalloc((void**)&d_dist, std::max(n, 1) * 4), "sort dist");
-    if (!s) s = check_hip(c, hipMalloc((void**)&d_order, std::max(n, 1) * 4), "sort order");
+    DevBuf<float> d_dist;
+    DevBuf<int> d_order;
+    rgbd_status s = check_hip(c, d_dist.alloc(n), "sort dist");
+    if (!s) s = check_hip(c, d_order.alloc(n), "sort order");
     if (!s) s = check_hip(c, hipMemcpy(d_dist, dist, (size_t)n * 4, hipMemcpyHostToDevice), "sort in");
     if (!s) {
         s = check_hip(c, launch_lane_sort_test(d_dist, n, depth_limit, d_order, c->stream), "launch of k_lane_sort_test");
     }
     if (!s) s = check_hip(c, hipMemcpyAsync(order, d_order, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream), "sort out");
-    if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "sort sync");
-    if (d_dist) (void)hipFree(d_dist);
-    if (d_order) (void)hipFree(d_order);
-    return s;
+    return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "sort sync");
 }
 
 }  // namespace rgbd

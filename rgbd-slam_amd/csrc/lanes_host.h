@@ -22,5 +22,6 @@ rgbd_status lanes_track(rgbd_ctx* c, int B, float nnratio, const rgbd_ransac_par
                         std::vector<PairOut>& out, uint8_t* flags_out2, uint8_t* flags_out1);
 rgbd_status lanes_sort_test(rgbd_ctx* c, const float* dist, int n, int depth_limit, int* order);
 void lanes_free(rgbd_ctx* c);
+void raster_consts(double* rcx, double* rcy);   // RansacSE3's raster constants (Solver/SolverSE3.cpp:218-225)
 
 }  // namespace rgbd

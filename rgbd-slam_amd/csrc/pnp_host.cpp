@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "context.h"
@@ -108,31 +109,6 @@ constexpr int kPnpFirstChunk = 8, kPnpFirstChunk2 = 16;   // the first solve's c
 constexpr int kPnpChunkMin = 4, kPnpChunkMax = 64;
 constexpr int kChainRngTab = 8192;   // raw RNG outputs tabulated for k_pnp_chain (~1600 iterations at 400 points)
 
-
-template <typename T>
-rgbd_status grow_dev(rgbd_ctx* c, T** p, size_t* cap, size_t need, const char* what)
-{
-    if (need <= *cap) return RGBD_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    const size_t n = std::max(need, *cap * 2);
-    rgbd_status s = check_hip(c, hipMalloc((void**)p, n * sizeof(T)), what);
-    *cap = s ? 0 : n;
-    return s;
-}
-
-template <typename T>
-rgbd_status grow_host(rgbd_ctx* c, T** p, size_t* cap, size_t need, const char* what)
-{
-    if (need <= *cap) return RGBD_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    const size_t n = std::max(need, *cap * 2);
-    rgbd_status s = check_hip(c, hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault), what);
-    *cap = s ? 0 : n;
-    return s;
-}
-
 }  // namespace
 
 struct PnpWS {
@@ -140,59 +116,38 @@ struct PnpWS {
     int k0 = 0, k1 = 0;     // subsets per problem of the two device chunks (fixed when the subsets are drawn)
     bool sampled = false;   // the first chunk's subsets are drawn (pnp_sample_launch), the rest not launched yet
     // device
-    float* d_p3 = nullptr; size_t c_p3 = 0;
-    float* d_p2 = nullptr; size_t c_p2 = 0;
-    uint8_t* d_mask = nullptr; size_t c_mask = 0;
-    int* d_mq = nullptr; size_t c_mq = 0;
-    int* d_mt = nullptr; size_t c_mt = 0;
-    PnpProbDev* d_probs = nullptr; size_t c_probs = 0;
-    int* d_hprob = nullptr; size_t c_hprob = 0;      // hypothesis -> problem
-    int* d_samples = nullptr; size_t c_samples = 0;
-    int* d_good = nullptr; size_t c_good = 0;
-    PnpModel* d_models = nullptr; size_t c_models = 0;
-    int* d_best = nullptr; size_t c_best = 0;        // [best | force_all] per problem
-    int* d_cpairs = nullptr;   // consecutive pairs (b-1, b) for b < maxB: [query frames | train frames]
+    DevBuf<float> d_p3, d_p2;
+    DevBuf<uint8_t> d_mask;
+    DevBuf<int> d_mq, d_mt;
+    DevBuf<PnpProbDev> d_probs;
+    DevBuf<int> d_hprob;       // hypothesis -> problem
+    DevBuf<int> d_samples, d_good;
+    DevBuf<PnpModel> d_models;
+    DevBuf<int> d_best;        // [best | force_all] per problem
+    DevBuf<int> d_cpairs;      // consecutive pairs (b-1, b) for b < maxB: [query frames | train frames]
     // per-problem results in one block [rep | out] (device and pinned host), read back by one copy
-    unsigned char* d_res = nullptr; unsigned char* h_res = nullptr; size_t c_res = 0;
-    PnpRep* d_rep = nullptr; PnpModel* d_out = nullptr;
+    DevBuf<unsigned char> d_res;
+    PinnedBuf<unsigned char> h_res;
+    PnpRep *d_rep = nullptr, *h_rep = nullptr;     // the two typed views of each block
+    PnpModel *d_out = nullptr, *h_out = nullptr;
     // pinned host mirrors
-    PnpProbDev* h_probs = nullptr; size_t ch_probs = 0;
-    int* h_hprob = nullptr; size_t ch_hprob = 0;
-    int* h_samples = nullptr; size_t ch_samples = 0;
-    int* h_good = nullptr; size_t ch_good = 0;
-    int* h_best = nullptr; size_t ch_best = 0;
-    PnpRep* h_rep = nullptr; PnpModel* h_out = nullptr;
+    PinnedBuf<PnpProbDev> h_probs;
+    PinnedBuf<int> h_hprob, h_samples, h_good, h_best;
     // outlier-flag chain (rgbd_pnp_params.flag_segments > 0): per-frame mvbOutlier rows, the runs' first
     // pairs, the per-pair results (k_pnp_chain) and the per-frame extraction error flags
-    uint8_t* d_flags = nullptr; size_t c_flags = 0;
-    int* d_seg = nullptr; size_t c_seg = 0;
-    int* h_seg = nullptr; size_t ch_seg = 0;
-    PnpChainRes* d_cres = nullptr; size_t c_cres = 0;
-    PnpChainRes* h_cres = nullptr; size_t ch_cres = 0;
-    uint32_t* d_rngtab = nullptr;   // the raw cv::RNG((uint64)-1) stream (kChainRngTab outputs)
-    int* h_err = nullptr; size_t ch_err = 0;
-    hipEvent_t ev = nullptr;   // recorded after the first-chunk read-back (pnp_launch)
-    hipEvent_t ev_in = nullptr;   // recorded on the extraction stream after the 3D-2D gather
+    DevBuf<uint8_t> d_flags;
+    DevBuf<int> d_seg;
+    PinnedBuf<int> h_seg;
+    DevBuf<PnpChainRes> d_cres;
+    PinnedBuf<PnpChainRes> h_cres;
+    DevBuf<uint32_t> d_rngtab;   // the raw cv::RNG((uint64)-1) stream (kChainRngTab outputs)
+    PinnedBuf<int> h_err;
+    Event ev;      // recorded after the first-chunk read-back (pnp_launch)
+    Event ev_in;   // recorded on the extraction stream after the 3D-2D gather
     hipStream_t st = nullptr;     // solve stream: nullptr = the context stream
 };
 
 static hipStream_t ws_stream(const rgbd_ctx* c, const PnpWS* w) { return w->st ? w->st : c->stream; }
-
-static void ws_free(PnpWS* w)
-{
-    if (!w) return;
-    void* dev[] = {w->d_p3, w->d_p2, w->d_mask, w->d_mq, w->d_mt, w->d_probs, w->d_hprob, w->d_samples,
-                   w->d_good, w->d_models, w->d_best, w->d_res, w->d_cpairs, w->d_flags, w->d_seg, w->d_cres, w->d_rngtab};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    void* host[] = {w->h_probs, w->h_hprob, w->h_samples, w->h_good, w->h_best, w->h_res, w->h_seg, w->h_cres,
-                    w->h_err};
-    for (void* p : host)
-        if (p) (void)hipHostFree(p);
-    if (w->ev) (void)hipEventDestroy(w->ev);
-    if (w->ev_in) (void)hipEventDestroy(w->ev_in);
-    delete w;
-}
 
 // submit / collect tracking: kPipeDepth workspaces used in turn, submissions collected in order.
 // A submission's PnPRansac solve is launched (on the solve stream) by the NEXT submission right after
@@ -200,17 +155,9 @@ static void ws_free(PnpWS* w)
 // quadtree / blur / description kernels, not beside the VALU-bound FAST.  collect launches a solve
 // still due itself.
 constexpr int kPipeDepth = 3;
-// the per-batch extraction outputs a step's knn-2 / gather read: consecutive pipelined submissions
+// the per-batch extraction outputs a step's knn-2 / gather read (OutSet): consecutive pipelined submissions
 // alternate between the context's own set (0) and a second one (1), so step i's matching (on the
-// match stream) overlaps step i+1's extraction
-struct OutSet {
-    int* count = nullptr;
-    float* kps = nullptr;
-    float* kun = nullptr;
-    uint8_t* desc = nullptr;
-    float* xyz = nullptr;
-    int4* knn = nullptr;
-};
+// match stream) overlaps step i+1's extraction.  c->out is the set of the latest submission.
 struct PnpPending {
     int B = 0, P = 0;
     rgbd_pnp_params prm{};
@@ -224,74 +171,48 @@ struct PnpPipe {
     PnpPending q[kPipeDepth];
     int head = 0;    // slot of the oldest outstanding submission
     int count = 0;   // outstanding submissions (0..kPipeDepth)
-    hipEvent_t ev_fast = nullptr;   // recorded on the launch stream after a submission's k_fast
+    Event ev_fast;   // recorded on the launch stream after a submission's k_fast
+    OutBufs second;  // output set 1 (set 0 is the context's own)
     OutSet set[2];
-    int parity = 0;                 // output set of the next submission
-    hipEvent_t ev_free[2] = {};     // recorded on the match stream after the last gather reading a set
-    hipEvent_t ev_desc = nullptr;   // recorded on the launch stream after a submission's extraction
+    int parity = 0;      // output set of the next submission
+    Event ev_free[2];    // recorded on the match stream after the last gather reading a set
+    Event ev_desc;       // recorded on the launch stream after a submission's extraction
+    ~PnpPipe() { for (PnpWS* w : ws) delete w; }
 };
-
-static OutSet ctx_outputs(const rgbd_ctx* c) { return OutSet{c->d_count, c->d_kps, c->d_kun, c->d_desc, c->d_xyz, c->d_knn}; }
-static void set_ctx_outputs(rgbd_ctx* c, const OutSet& o)
-{
-    c->d_count = o.count;
-    c->d_kps = o.kps;
-    c->d_kun = o.kun;
-    c->d_desc = o.desc;
-    c->d_xyz = o.xyz;
-    c->d_knn = o.knn;
-}
 
 void pnp_free(rgbd_ctx* c)
 {
-    ws_free(static_cast<PnpWS*>(c->pnp));
+    delete c->pnp;
+    delete c->pnp_pipe;
     c->pnp = nullptr;
-    if (PnpPipe* pp = static_cast<PnpPipe*>(c->pnp_pipe)) {
-        for (PnpWS* w : pp->ws) ws_free(w);
-        if (pp->ev_fast) (void)hipEventDestroy(pp->ev_fast);
-        if (pp->ev_desc) (void)hipEventDestroy(pp->ev_desc);
-        for (hipEvent_t e : pp->ev_free)
-            if (e) (void)hipEventDestroy(e);
-        if (pp->set[0].count) set_ctx_outputs(c, pp->set[0]);   // the context frees its own set
-        const OutSet& a = pp->set[1];
-        void* ptrs[] = {a.count, a.kps, a.kun, a.desc, a.xyz, a.knn};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        delete pp;
-        c->pnp_pipe = nullptr;
-    }
+    c->pnp_pipe = nullptr;
 }
 
 static PnpWS* pnp_ws(rgbd_ctx* c)
 {
     if (!c->pnp) c->pnp = new PnpWS();
-    return static_cast<PnpWS*>(c->pnp);
+    return c->pnp;
 }
 
 static rgbd_status ws_points(rgbd_ctx* c, PnpWS* w, size_t npts, size_t P)
 {
-    rgbd_status s = grow_dev(c, &w->d_p3, &w->c_p3, 3 * std::max<size_t>(npts, 1), "pnp p3");
-    if (!s) s = grow_dev(c, &w->d_p2, &w->c_p2, 2 * std::max<size_t>(npts, 1), "pnp p2");
-    if (!s) s = grow_dev(c, &w->d_mask, &w->c_mask, std::max<size_t>(npts, 1), "pnp mask");
-    if (!s) s = grow_dev(c, &w->d_probs, &w->c_probs, std::max<size_t>(P, 1), "pnp probs");
-    if (!s) s = grow_dev(c, &w->d_best, &w->c_best, 2 * std::max<size_t>(P, 1), "pnp best");
-    if (!s) s = grow_host(c, &w->h_probs, &w->ch_probs, std::max<size_t>(P, 1), "pnp h probs");
-    if (!s) s = grow_host(c, &w->h_best, &w->ch_best, 2 * std::max<size_t>(P, 1), "pnp h best");
-    if (!s && P > w->c_res) {
+    rgbd_status s = check_hip(c, w->d_p3.reserve(3 * std::max<size_t>(npts, 1)), "pnp p3");
+    if (!s) s = check_hip(c, w->d_p2.reserve(2 * std::max<size_t>(npts, 1)), "pnp p2");
+    if (!s) s = check_hip(c, w->d_mask.reserve(std::max<size_t>(npts, 1)), "pnp mask");
+    if (!s) s = check_hip(c, w->d_probs.reserve(std::max<size_t>(P, 1)), "pnp probs");
+    if (!s) s = check_hip(c, w->d_best.reserve(2 * std::max<size_t>(P, 1)), "pnp best");
+    if (!s) s = check_hip(c, w->h_probs.reserve(std::max<size_t>(P, 1)), "pnp h probs");
+    if (!s) s = check_hip(c, w->h_best.reserve(2 * std::max<size_t>(P, 1)), "pnp h best");
+    constexpr size_t per = sizeof(PnpRep) + sizeof(PnpModel);
+    if (!s && P > std::min(w->d_res.capacity(), w->h_res.capacity()) / per) {   // both blocks or neither count
         const size_t n = std::max<size_t>(P, 1);
-        const size_t bytes = n * (sizeof(PnpRep) + sizeof(PnpModel));
         static_assert(sizeof(PnpRep) % alignof(PnpModel) == 0, "results block alignment");
-        if (w->d_res) (void)hipFree(w->d_res);
-        if (w->h_res) (void)hipHostFree(w->h_res);
-        w->d_res = w->h_res = nullptr;
-        w->c_res = 0;
-        s = check_hip(c, hipMalloc((void**)&w->d_res, bytes), "pnp results");
-        if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_res, bytes, hipHostMallocDefault), "pnp h results");
+        s = check_hip(c, w->d_res.alloc(n * per), "pnp results");
+        if (!s) s = check_hip(c, w->h_res.alloc(n * per), "pnp h results");
         if (s) return s;
-        w->c_res = n;
-        w->d_rep = reinterpret_cast<PnpRep*>(w->d_res);
+        w->d_rep = reinterpret_cast<PnpRep*>(w->d_res.get());
         w->d_out = reinterpret_cast<PnpModel*>(w->d_res + n * sizeof(PnpRep));
-        w->h_rep = reinterpret_cast<PnpRep*>(w->h_res);
+        w->h_rep = reinterpret_cast<PnpRep*>(w->h_res.get());
         w->h_out = reinterpret_cast<PnpModel*>(w->h_res + n * sizeof(PnpRep));
     }
     return s;
@@ -308,26 +229,19 @@ struct PnpResult {
 // grow the hypothesis arrays (good, models) to `need` slots, keeping the first `keep` models
 static rgbd_status grow_hyp(rgbd_ctx* c, PnpWS* w, size_t need, size_t keep)
 {
-    if (need <= w->c_good) return RGBD_OK;
-    const size_t n = std::max(need, w->c_good * 2);
-    int* ng = nullptr;
-    PnpModel* nm = nullptr;
-    rgbd_status s = check_hip(c, hipMalloc((void**)&ng, n * sizeof(int)), "pnp good");
-    if (!s) s = check_hip(c, hipMalloc((void**)&nm, n * sizeof(PnpModel)), "pnp models");
+    if (need <= w->d_good.capacity()) return RGBD_OK;
+    const size_t n = std::max(need, w->d_good.capacity() * 2);
+    DevBuf<int> ng;
+    DevBuf<PnpModel> nm;
+    rgbd_status s = check_hip(c, ng.alloc(n), "pnp good");
+    if (!s) s = check_hip(c, nm.alloc(n), "pnp models");
     if (!s && keep > 0) {
         s = check_hip(c, hipMemcpyAsync(nm, w->d_models, keep * sizeof(PnpModel), hipMemcpyDeviceToDevice, ws_stream(c, w)), "pnp models copy");
         if (!s) s = check_hip(c, hipStreamSynchronize(ws_stream(c, w)), "sync");
     }
-    if (s) {
-        if (ng) (void)hipFree(ng);
-        if (nm) (void)hipFree(nm);
-        return s;
-    }
-    if (w->d_good) (void)hipFree(w->d_good);
-    if (w->d_models) (void)hipFree(w->d_models);
-    w->d_good = ng;
-    w->d_models = nm;
-    w->c_good = w->c_models = n;
+    if (s) return s;
+    w->d_good = std::move(ng);
+    w->d_models = std::move(nm);
     return RGBD_OK;
 }
 
@@ -366,8 +280,8 @@ static rgbd_status pnp_sample_launch(rgbd_ctx* c, PnpWS* w, int P, const rgbd_pn
     const int H01 = P * (w->k0 + w->k1);
     w->h01 = H01;   // pnp_finish's host continuation writes its hypotheses after both chunks
     rgbd_status s = grow_hyp(c, w, (size_t)std::max(H01, 1), 0);
-    if (!s) s = grow_dev(c, &w->d_hprob, &w->c_hprob, (size_t)std::max(H01, 1), "pnp hprob");
-    if (!s) s = grow_dev(c, &w->d_samples, &w->c_samples, (size_t)std::max(H01, 1) * kPnpModel, "pnp samples");
+    if (!s) s = check_hip(c, w->d_hprob.reserve((size_t)std::max(H01, 1)), "pnp hprob");
+    if (!s) s = check_hip(c, w->d_samples.reserve((size_t)std::max(H01, 1) * kPnpModel), "pnp samples");
     if (s) return s;
     const int tk = timer_begin(c, "k_pnp_sample", st);
     RGBD_TRY(c, launch_pnp_sample(w->d_probs, P, dp, w->d_samples, w->d_hprob, w->d_rep, st), "pnp_sample");
@@ -411,9 +325,9 @@ static rgbd_status pnp_launch(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
                       w->d_out, st), "pnp_refine");
     timer_end(c, tk);
     // replay states and refined models in one copy
-    s = check_hip(c, hipMemcpyAsync(w->h_res, w->d_res, w->c_res * (sizeof(PnpRep) + sizeof(PnpModel)),
+    s = check_hip(c, hipMemcpyAsync(w->h_res, w->d_res, w->d_res.capacity(),
                                         hipMemcpyDeviceToHost, st), "results");
-    if (!s && !w->ev) s = check_hip(c, hipEventCreateWithFlags(&w->ev, hipEventDisableTiming), "pnp event");
+    if (!s) s = check_hip(c, w->ev.ensure(), "pnp event");
     if (!s) s = check_hip(c, hipEventRecord(w->ev, st), "pnp event record");
     return s;
 }
@@ -474,11 +388,11 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
         int H = 0;
         for (const Run& u : run)
             if (u.iter < u.niters) H += std::min(u.chunk, u.niters - u.evaluated);
-        s = grow_host(c, &w->h_hprob, &w->ch_hprob, (size_t)H, "pnp h hprob");
-        if (!s) s = grow_host(c, &w->h_samples, &w->ch_samples, (size_t)H * kPnpModel, "pnp h samples");
-        if (!s) s = grow_host(c, &w->h_good, &w->ch_good, (size_t)H, "pnp h good");
-        if (!s) s = grow_dev(c, &w->d_hprob, &w->c_hprob, (size_t)H, "pnp hprob");
-        if (!s) s = grow_dev(c, &w->d_samples, &w->c_samples, (size_t)H * kPnpModel, "pnp samples");
+        s = check_hip(c, w->h_hprob.reserve((size_t)H), "pnp h hprob");
+        if (!s) s = check_hip(c, w->h_samples.reserve((size_t)H * kPnpModel), "pnp h samples");
+        if (!s) s = check_hip(c, w->h_good.reserve((size_t)H), "pnp h good");
+        if (!s) s = check_hip(c, w->d_hprob.reserve((size_t)H), "pnp hprob");
+        if (!s) s = check_hip(c, w->d_samples.reserve((size_t)H * kPnpModel), "pnp samples");
         if (!s) s = grow_hyp(c, w, (size_t)Htot + H, (size_t)Htot);
         if (s) return s;
         int h = 0;
@@ -651,14 +565,13 @@ static rgbd_status track_submit(rgbd_ctx* c, PnpWS* w, const void* d_bgr, const 
     rgbd_status s = extract_batch(c, d_bgr, d_depth, B, after_fast);
     if (s) return s;
     // per-frame capacity flags of this extraction, read by collect (ordered before every later event)
-    if ((s = grow_host(c, &w->h_err, &w->ch_err, (size_t)B, "pnp h err"))) return s;
+    if ((s = check_hip(c, w->h_err.reserve((size_t)B), "pnp h err"))) return s;
     if ((s = check_hip(c, hipMemcpyAsync(w->h_err, c->d_err, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream), "err")))
         return s;
     // pipelined: knn-2 + gather on the match stream, after this extraction (event)
     if (pp && (s = check_hip(c, hipEventRecord(pp->ev_desc, c->stream), "extraction event"))) return s;
-    const OutSet o = pp ? pp->set[set] : ctx_outputs(c);
     if ((s = match_launch(c, w, B, nnratio, segments, pp, set))) return s;
-    return segments > 0 ? flag_chain_launch(c, w, o, B, nnratio, prm) : RGBD_OK;
+    return segments > 0 ? flag_chain_launch(c, w, c->out, B, nnratio, prm) : RGBD_OK;
 }
 
 // knn-2 (+ the Matcher filter and 3D-2D gather) of a submission's consecutive pairs, reading output set
@@ -668,18 +581,11 @@ static rgbd_status match_launch(rgbd_ctx* c, PnpWS* w, int B, float nnratio, int
     const int K = c->cfg.kp_cap;
     rgbd_status s = RGBD_OK;
     hipStream_t st = c->stream;
-    OutSet cur{};
-    if (pp) {
+    if (pp) {   // c->out is pp->set[set]: the submission selected it before its extraction
         s = check_hip(c, hipStreamWaitEvent(c->match_stream, pp->ev_desc, 0), "extraction wait");
         if (s) return s;
         st = c->match_stream;
-        cur = ctx_outputs(c);
-        set_ctx_outputs(c, pp->set[set]);
     }
-    struct Restore {
-        rgbd_ctx* c; PnpPipe* pp; OutSet o;
-        ~Restore() { if (pp) set_ctx_outputs(c, o); }
-    } restore{c, pp, cur};
     const int P = B - 1;
     if (P == 0) return RGBD_OK;
     if (!w->d_cpairs) {   // written once: the layout does not depend on B
@@ -688,30 +594,30 @@ static rgbd_status match_launch(rgbd_ctx* c, PnpWS* w, int B, float nnratio, int
             pairs[p] = p;                 // query = reference frame b-1
             pairs[c->maxB + p] = p + 1;   // train = current frame b
         }
-        s = check_hip(c, hipMalloc((void**)&w->d_cpairs, pairs.size() * 4), "pnp pairs");
+        s = check_hip(c, w->d_cpairs.alloc(pairs.size()), "pnp pairs");
         if (!s) s = check_hip(c, hipMemcpy(w->d_cpairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice), "pairs");
         if (s) return s;
     }
     int tk = timer_begin(c, "k_knn2", st);
-    RGBD_TRY(c, launch_knn2(c->d_desc, c->d_count, w->d_cpairs, w->d_cpairs + c->maxB, K, K, c->d_knn, P, st), "knn2");
+    RGBD_TRY(c, launch_knn2(c->out.desc, c->out.count, w->d_cpairs, w->d_cpairs + c->maxB, K, K, c->out.knn, P, st), "knn2");
     timer_end(c, tk);
     if (segments > 0) {   // the flag chain waits for the knn-2 rows (flag_chain_launch)
-        if (!w->ev_in) s = check_hip(c, hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming), "pnp knn event");
+        s = check_hip(c, w->ev_in.ensure(), "pnp knn event");
         if (!s) s = check_hip(c, hipEventRecord(w->ev_in, st), "pnp knn record");
         return s;
     }
     if ((s = ws_points(c, w, (size_t)P * K, (size_t)P))) return s;
-    if ((s = grow_dev(c, &w->d_mq, &w->c_mq, (size_t)P * K, "pnp mq"))) return s;
-    if ((s = grow_dev(c, &w->d_mt, &w->c_mt, (size_t)P * K, "pnp mt"))) return s;
+    if ((s = check_hip(c, w->d_mq.reserve((size_t)P * K), "pnp mq"))) return s;
+    if ((s = check_hip(c, w->d_mt.reserve((size_t)P * K), "pnp mt"))) return s;
     tk = timer_begin(c, "k_match_gather", st);
-    RGBD_TRY(c, launch_match_gather(c->d_knn, c->d_count, w->d_cpairs, w->d_cpairs + c->maxB, c->d_xyz, c->d_kun, K, nnratio, P,
+    RGBD_TRY(c, launch_match_gather(c->out.knn, c->out.count, w->d_cpairs, w->d_cpairs + c->maxB, c->out.xyz, c->out.kun, K, nnratio, P,
                         w->d_p3, w->d_p2, w->d_probs, w->d_mq, w->d_mt, st), "match_gather");
     timer_end(c, tk);
     // pipelined: the first chunk's subsets right behind the gather on this stream, so the solve stream's
     // chain starts at the hypotheses (a one-workgroup kernel launched beside the quadtree waits for a
     // free wave slot)
     if (w->st && w->st != st) {   // the solve waits for this step's gather (pnp_solve_launch)
-        if (!w->ev_in) s = check_hip(c, hipEventCreateWithFlags(&w->ev_in, hipEventDisableTiming), "pnp gather event");
+        s = check_hip(c, w->ev_in.ensure(), "pnp gather event");
         if (!s) s = check_hip(c, hipEventRecord(w->ev_in, st), "pnp gather record");
     }
     if (!s && pp) s = check_hip(c, hipEventRecord(pp->ev_free[set], st), "output set free record");
@@ -747,14 +653,14 @@ static rgbd_status flag_chain_launch(rgbd_ctx* c, PnpWS* w, const OutSet& o, int
     if (P <= 0) return RGBD_OK;
     const int S = std::max(1, std::min(prm.flag_segments, P));
     const hipStream_t st = ws_stream(c, w);
-    rgbd_status s = grow_host(c, &w->h_seg, &w->ch_seg, (size_t)S + 1, "flag runs h");
-    if (!s) s = grow_dev(c, &w->d_seg, &w->c_seg, (size_t)S + 1, "flag runs");
-    if (!s) s = grow_host(c, &w->h_cres, &w->ch_cres, (size_t)P, "flag results h");
-    if (!s) s = grow_dev(c, &w->d_cres, &w->c_cres, (size_t)P, "flag results");
-    if (!s) s = grow_dev(c, &w->d_flags, &w->c_flags, (size_t)B * K, "flags");
+    rgbd_status s = check_hip(c, w->h_seg.reserve((size_t)S + 1), "flag runs h");
+    if (!s) s = check_hip(c, w->d_seg.reserve((size_t)S + 1), "flag runs");
+    if (!s) s = check_hip(c, w->h_cres.reserve((size_t)P), "flag results h");
+    if (!s) s = check_hip(c, w->d_cres.reserve((size_t)P), "flag results");
+    if (!s) s = check_hip(c, w->d_flags.reserve((size_t)B * K), "flags");
     if (!s) s = ws_points(c, w, (size_t)P * K, (size_t)P);
-    if (!s) s = grow_dev(c, &w->d_mq, &w->c_mq, (size_t)P * K, "pnp mq");
-    if (!s) s = grow_dev(c, &w->d_mt, &w->c_mt, (size_t)P * K, "pnp mt");
+    if (!s) s = check_hip(c, w->d_mq.reserve((size_t)P * K), "pnp mq");
+    if (!s) s = check_hip(c, w->d_mt.reserve((size_t)P * K), "pnp mt");
     if (!s) s = grow_hyp(c, w, (size_t)P, 0);
     if (s) return s;
     // the first kChainRngTab raw outputs of cv::RNG((uint64)-1), shared by every solvePnPRansac call
@@ -762,7 +668,7 @@ static rgbd_status flag_chain_launch(rgbd_ctx* c, PnpWS* w, const OutSet& o, int
     if (!w->d_rngtab) {
         std::vector<uint32_t> tab(kChainRngTab);
         for (int j = 0; j < kChainRngTab; j++) tab[j] = gen.next();
-        s = check_hip(c, hipMalloc((void**)&w->d_rngtab, tab.size() * 4), "rng table");
+        s = check_hip(c, w->d_rngtab.alloc(tab.size()), "rng table");
         if (!s) s = check_hip(c, hipMemcpy(w->d_rngtab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice), "rng table");
         if (s) return s;
     } else {
@@ -793,7 +699,7 @@ static rgbd_status flag_chain_launch(rgbd_ctx* c, PnpWS* w, const OutSet& o, int
     if (!s)
         s = check_hip(c, hipMemcpyAsync(w->h_out, w->d_out, (size_t)P * sizeof(PnpModel), hipMemcpyDeviceToHost, st),
                       "flag models");
-    if (!s && !w->ev) s = check_hip(c, hipEventCreateWithFlags(&w->ev, hipEventDisableTiming), "pnp event");
+    if (!s) s = check_hip(c, w->ev.ensure(), "pnp event");
     if (!s) s = check_hip(c, hipEventRecord(w->ev, st), "pnp event record");
     return s;
 }
@@ -875,7 +781,7 @@ rgbd_status rgbd_pnp_track_batch(rgbd_ctx* c, const void* d_bgr, const void* d_d
     PnpWS* w = pnp_ws(c);
     rgbd_status s = track_submit(c, w, d_bgr, d_depth, B, nnratio, *prm);
     if (!s && prm->flag_segments == 0) s = pnp_solve_launch(c, w, B - 1, *prm);
-    return s ? s : track_collect(c, w, B, nnratio, *prm, ctx_outputs(c), poses, status, n_inliers, n_matches);
+    return s ? s : track_collect(c, w, B, nnratio, *prm, c->out, poses, status, n_inliers, n_matches);
 }
 
 rgbd_status rgbd_pnp_track_submit(rgbd_ctx* c, const void* d_bgr, const void* d_depth, int32_t B, float nnratio,
@@ -884,7 +790,7 @@ rgbd_status rgbd_pnp_track_submit(rgbd_ctx* c, const void* d_bgr, const void* d_
     if (!c || !d_bgr || !d_depth || B < 1 || !prm || prm->flag_segments < 0) return RGBD_ERR_ARG;
     if (B > c->maxB) return fail(c, RGBD_ERR_CAPACITY, "batch larger than max_batch");
     if (!c->pnp_pipe) c->pnp_pipe = new PnpPipe();
-    PnpPipe* pp = static_cast<PnpPipe*>(c->pnp_pipe);
+    PnpPipe* pp = c->pnp_pipe;
     if (pp->count >= kPipeDepth) return fail(c, RGBD_ERR_ARG, "three submissions outstanding: collect first");
     // flag chain: an output set is read until its collect's last round, so a set comes back only after
     // that collect (two output sets -> at most two outstanding)
@@ -900,22 +806,22 @@ rgbd_status rgbd_pnp_track_submit(rgbd_ctx* c, const void* d_bgr, const void* d_
         s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
         if (!s && c->serial) c->solve_stream = c->own_stream;
         else if (!s) s = check_hip(c, hipStreamCreateWithPriority(&c->solve_stream, hipStreamNonBlocking, hi), "solve stream");
-        if (!s) s = check_hip(c, hipEventCreateWithFlags(&pp->ev_fast, hipEventDisableTiming), "pipe event");
+        if (!s) s = check_hip(c, pp->ev_fast.ensure(), "pipe event");
         if (s) return s;
     }
     if (!c->match_stream) {   // the second output set, the match stream and its events
         const size_t Bm = (size_t)c->maxB, K = (size_t)c->cfg.kp_cap;
-        OutSet& a = pp->set[1];
-        pp->set[0] = ctx_outputs(c);
-        s = check_hip(c, hipMalloc((void**)&a.count, std::max<size_t>(Bm * 4, 16)), "set count");
-        if (!s) s = check_hip(c, hipMalloc((void**)&a.kps, Bm * K * 28), "set kps");
-        if (!s) s = check_hip(c, hipMalloc((void**)&a.kun, Bm * K * 28), "set kun");
-        if (!s) s = check_hip(c, hipMalloc((void**)&a.desc, Bm * K * 32), "set desc");
-        if (!s) s = check_hip(c, hipMalloc((void**)&a.xyz, Bm * K * 12), "set xyz");
-        if (!s) s = check_hip(c, hipMalloc((void**)&a.knn, Bm * K * sizeof(int4)), "set knn");
-        for (int k = 0; !s && k < 2; k++)
-            s = check_hip(c, hipEventCreateWithFlags(&pp->ev_free[k], hipEventDisableTiming), "set event");
-        if (!s) s = check_hip(c, hipEventCreateWithFlags(&pp->ev_desc, hipEventDisableTiming), "extraction event");
+        OutBufs& a = pp->second;
+        s = check_hip(c, a.count.alloc(Bm), "set count");
+        if (!s) s = check_hip(c, a.kps.alloc(Bm * K * 7), "set kps");
+        if (!s) s = check_hip(c, a.kun.alloc(Bm * K * 7), "set kun");
+        if (!s) s = check_hip(c, a.desc.alloc(Bm * K * 32), "set desc");
+        if (!s) s = check_hip(c, a.xyz.alloc(Bm * K * 3), "set xyz");
+        if (!s) s = check_hip(c, a.knn.alloc(Bm * K), "set knn");
+        pp->set[0] = c->own_out.view();
+        pp->set[1] = a.view();
+        for (int k = 0; !s && k < 2; k++) s = check_hip(c, pp->ev_free[k].ensure(), "set event");
+        if (!s) s = check_hip(c, pp->ev_desc.ensure(), "extraction event");
         if (!s && c->serial) c->match_stream = c->own_stream;
         else if (!s) {   // the match stream at the lowest priority
             int lo = 0, hi = 0;
@@ -927,7 +833,7 @@ rgbd_status rgbd_pnp_track_submit(rgbd_ctx* c, const void* d_bgr, const void* d_
     // this submission's output set: wait until the gather that last read it has run
     const int set = pp->parity;
     pp->parity ^= 1;
-    set_ctx_outputs(c, pp->set[set]);
+    c->out = pp->set[set];
     if ((s = check_hip(c, hipStreamWaitEvent(c->stream, pp->ev_free[set], 0), "output set wait"))) return s;
     if (!pp->ws[slot]) pp->ws[slot] = new PnpWS();
     pp->ws[slot]->st = c->solve_stream;
@@ -970,7 +876,7 @@ rgbd_status rgbd_pnp_track_submit(rgbd_ctx* c, const void* d_bgr, const void* d_
 rgbd_status rgbd_pnp_track_collect(rgbd_ctx* c, float* poses, int32_t* status, int32_t* n_inliers, int32_t* n_matches)
 {
     if (!c || !poses || !status) return RGBD_ERR_ARG;
-    PnpPipe* pp = static_cast<PnpPipe*>(c->pnp_pipe);
+    PnpPipe* pp = c->pnp_pipe;
     if (!pp || pp->count == 0) return fail(c, RGBD_ERR_ARG, "nothing submitted");
     const int slot = pp->head;
     PnpPending& q = pp->q[slot];

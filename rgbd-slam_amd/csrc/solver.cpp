@@ -30,59 +30,43 @@ namespace rgbd {
 struct RansacWS {
     int capM = 0, capH = 0, MWcap = 0;
     // device: [pts 6*capM f32][samples capH*8 i32][scount capH i32] and [out capH HypOut][masks capH*MWcap u32]
-    unsigned char* d_in = nullptr;
-    unsigned char* d_res = nullptr;
-    unsigned char* h_in = nullptr;    // pinned mirrors
-    unsigned char* h_res = nullptr;
-    size_t in_bytes = 0, res_bytes = 0;
-    float* pts() { return reinterpret_cast<float*>(h_in); }
+    DevBuf<unsigned char> d_in, d_res;
+    PinnedBuf<unsigned char> h_in, h_res;   // pinned mirrors
+    float* pts() { return reinterpret_cast<float*>(h_in.get()); }
     int* samples() { return reinterpret_cast<int*>(h_in + (size_t)capM * 24); }
     int* scount() { return samples() + (size_t)capH * 8; }
-    HypOut* out() { return reinterpret_cast<HypOut*>(h_res); }
+    HypOut* out() { return reinterpret_cast<HypOut*>(h_res.get()); }
     uint32_t* masks() { return reinterpret_cast<uint32_t*>(h_res + (size_t)capH * sizeof(HypOut)); }
     std::vector<rgbd_dmatch> used;
     std::vector<rgbd_rng> after;
 };
 
-static void ws_release(RansacWS* w)
-{
-    if (w->d_in) (void)hipFree(w->d_in);
-    if (w->d_res) (void)hipFree(w->d_res);
-    if (w->h_in) (void)hipHostFree(w->h_in);
-    if (w->h_res) (void)hipHostFree(w->h_res);
-    w->d_in = w->d_res = w->h_in = w->h_res = nullptr;
-}
-
 void ransac_free(rgbd_ctx* c)
 {
     lanes_free(c);
-    RansacWS* w = static_cast<RansacWS*>(c->ransac);
-    if (!w) return;
-    ws_release(w);
-    delete w;
+    delete c->ransac;
     c->ransac = nullptr;
 }
 
 static rgbd_status ransac_ws(rgbd_ctx* c, int M, int H, int SS, RansacWS** out)
 {
-    RansacWS* w = static_cast<RansacWS*>(c->ransac);
-    if (!w) {
-        w = new RansacWS();
-        c->ransac = w;
-    }
+    if (!c->ransac) c->ransac = new RansacWS();
+    RansacWS* w = c->ransac;
     const int needM = std::max(M, 1), needH = std::max(H, 1) + 1;
     if (needM > w->capM || needH > w->capH || SS > 8) {
-        ws_release(w);
-        w->capM = std::max(needM, std::max(w->capM, 1024));
-        w->capH = std::max(needH, std::max(w->capH, 256));
-        w->MWcap = (w->capM + 31) / 32 + 1;
-        w->in_bytes = (size_t)w->capM * 24 + (size_t)w->capH * 8 * 4 + (size_t)w->capH * 4;
-        w->res_bytes = (size_t)w->capH * sizeof(HypOut) + (size_t)w->capH * w->MWcap * 4;
-        rgbd_status s = check_hip(c, hipMalloc((void**)&w->d_in, w->in_bytes), "ransac in");
-        if (!s) s = check_hip(c, hipMalloc((void**)&w->d_res, w->res_bytes), "ransac res");
-        if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_in, w->in_bytes, hipHostMallocDefault), "ransac pinned in");
-        if (!s) s = check_hip(c, hipHostMalloc((void**)&w->h_res, w->res_bytes, hipHostMallocDefault), "ransac pinned res");
+        const int capM = std::max(needM, std::max(w->capM, 1024)), capH = std::max(needH, std::max(w->capH, 256));
+        const int MWcap = (capM + 31) / 32 + 1;
+        const size_t in_bytes = (size_t)capM * 24 + (size_t)capH * 8 * 4 + (size_t)capH * 4;
+        const size_t res_bytes = (size_t)capH * sizeof(HypOut) + (size_t)capH * MWcap * 4;
+        w->capM = w->capH = 0;   // no capacity until all four blocks are there
+        rgbd_status s = check_hip(c, w->d_in.alloc(in_bytes), "ransac in");
+        if (!s) s = check_hip(c, w->d_res.alloc(res_bytes), "ransac res");
+        if (!s) s = check_hip(c, w->h_in.alloc(in_bytes), "ransac pinned in");
+        if (!s) s = check_hip(c, w->h_res.alloc(res_bytes), "ransac pinned res");
         if (s) return s;
+        w->capM = capM;
+        w->capH = capH;
+        w->MWcap = MWcap;
     }
     *out = w;
     return RGBD_OK;
@@ -129,16 +113,6 @@ static int sample_ids(rgbd_rng* st, int M, int SS, int* ids)
         if (++safety > 10000) break;
     }
     return n;
-}
-
-static void raster_consts(double* rcx, double* rcy)
-{
-    const double cam_angle_x = 58.0 / 180.0 * M_PI;
-    const double cam_angle_y = 45.0 / 180.0 * M_PI;
-    const double sx = 3 * std::tan(cam_angle_x / 640.0);
-    const double sy = 3 * std::tan(cam_angle_y / 480.0);
-    *rcx = sx * sx;
-    *rcy = sy * sy;
 }
 
 static const int kFirstChunk = 24;   // hypotheses evaluated before the first replay
@@ -219,10 +193,10 @@ rgbd_status ransac_se3(rgbd_ctx* c, const float* xyz1, const float* xyz2, const 
     raster_consts(&dv.rcx, &dv.rcy);
     const hipStream_t st = c->stream;
     const int MW = (M + 31) / 32;
-    float* d_pts = reinterpret_cast<float*>(w->d_in);
+    float* d_pts = reinterpret_cast<float*>(w->d_in.get());
     int* d_samples = reinterpret_cast<int*>(w->d_in + (size_t)w->capM * 24);
     int* d_scount = d_samples + (size_t)w->capH * 8;
-    HypOut* d_out = reinterpret_cast<HypOut*>(w->d_res);
+    HypOut* d_out = reinterpret_cast<HypOut*>(w->d_res.get());
     uint32_t* d_masks = reinterpret_cast<uint32_t*>(w->d_res + (size_t)w->capH * sizeof(HypOut));
     int evaluated = 0;   // hypotheses [0, evaluated) done; a chunk's identity slot follows its last one
     bool pts_sent = false;
@@ -566,9 +540,9 @@ rgbd_status rgbd_debug_rotation_ops(rgbd_ctx* c, const double* x, const double* 
     if (!c || n < 1 || n > (1 << 24) || !x || !num || !den || !theta || !sq || !q || !t) return RGBD_ERR_ARG;
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
-    double* d = nullptr;
+    DevBuf<double> d;
     const size_t m = (size_t)n, bytes = m * sizeof(double);
-    s = check_hip(c, hipMalloc((void**)&d, 7 * bytes), "rotation ops buffers");
+    s = check_hip(c, d.alloc(7 * m), "rotation ops buffers");
     const double* in[4] = {x, num, den, theta};
     for (int k = 0; k < 4 && !s; k++)
         s = check_hip(c, hipMemcpyAsync(d + k * m, in[k], bytes, hipMemcpyHostToDevice, c->stream), "rotation ops in");
@@ -579,9 +553,7 @@ rgbd_status rgbd_debug_rotation_ops(rgbd_ctx* c, const double* x, const double* 
     double* out[3] = {sq, q, t};
     for (int k = 0; k < 3 && !s; k++)
         s = check_hip(c, hipMemcpyAsync(out[k], d + (4 + k) * m, bytes, hipMemcpyDeviceToHost, c->stream), "rotation ops out");
-    if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "rotation ops sync");
-    if (d) (void)hipFree(d);
-    return s;
+    return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "rotation ops sync");
 }
 
 rgbd_status rgbd_debug_sort_matches(rgbd_ctx* c, const float* dist, int32_t n, int32_t depth_limit, int32_t* order)

@@ -16,28 +16,28 @@
 
 namespace rgbd {
 
+struct SvoWS {
+    SvoCfg cfg{};
+    std::vector<SvoTile> tiles;
+    DevBuf<SvoTile> d_tiles;
+    DevBuf<uint8_t> d_pyr;
+    DevBuf<unsigned long long> d_cells;
+    DevBuf<uint16_t> d_box;
+    DevBuf<uint2> d_cand;
+    DevBuf<int> d_ncand;
+    DevBuf<uint32_t> d_pat;
+    DevBuf<float> d_rt_resp;   // rgbd_svo_retain_best staging
+    DevBuf<int> d_rt_order;
+    int8_t pattern[256 * 4];
+};
+
 namespace {
 
 const int8_t kDefaultBrief[256 * 4] = {
 #include "brief_pattern.inc"
 };
 
-struct SvoWS {
-    SvoCfg cfg{};
-    std::vector<SvoTile> tiles;
-    SvoTile* d_tiles = nullptr;
-    uint8_t* d_pyr = nullptr;
-    unsigned long long* d_cells = nullptr;
-    uint16_t* d_box = nullptr;
-    uint2* d_cand = nullptr;
-    int* d_ncand = nullptr;
-    uint32_t* d_pat = nullptr;
-    float* d_rt_resp = nullptr;   // rgbd_svo_retain_best staging
-    int* d_rt_order = nullptr;
-    int8_t pattern[256 * 4];
-};
-
-SvoWS* ws(rgbd_ctx* c) { return static_cast<SvoWS*>(c->svo); }
+SvoWS* ws(rgbd_ctx* c) { return c->svo; }
 
 rgbd_status upload_pattern(rgbd_ctx* c, SvoWS* w)
 {
@@ -101,16 +101,13 @@ rgbd_status svo_alloc(rgbd_ctx* c)
     SvoWS* w = ws(c);
     const SvoCfg& g = w->cfg;
     const size_t B = (size_t)c->maxB;
-    auto al = [&](auto** p, size_t bytes, const char* what) {
-        return check_hip(c, hipMalloc((void**)p, std::max<size_t>(bytes, 16)), what);
-    };
-    rgbd_status s = al(&w->d_tiles, w->tiles.size() * sizeof(SvoTile), "svo tiles");
-    if (!s) s = al(&w->d_pyr, B * g.frame_bytes + 64, "svo pyramid");
-    if (!s) s = al(&w->d_cells, B * g.ncells * 8, "svo cells");
-    if (!s) s = al(&w->d_box, B * g.W * g.H * 2, "svo box");
-    if (!s) s = al(&w->d_cand, B * g.ncells * 8, "svo candidates");
-    if (!s) s = al(&w->d_ncand, B * 4, "svo candidate counts");
-    if (!s) s = al(&w->d_pat, 256 * 4, "svo pattern");
+    rgbd_status s = check_hip(c, w->d_tiles.alloc(w->tiles.size()), "svo tiles");
+    if (!s) s = check_hip(c, w->d_pyr.alloc(B * g.frame_bytes + 64), "svo pyramid");
+    if (!s) s = check_hip(c, w->d_cells.alloc(B * g.ncells), "svo cells");
+    if (!s) s = check_hip(c, w->d_box.alloc(B * g.W * g.H), "svo box");
+    if (!s) s = check_hip(c, w->d_cand.alloc(B * g.ncells), "svo candidates");
+    if (!s) s = check_hip(c, w->d_ncand.alloc(B), "svo candidate counts");
+    if (!s) s = check_hip(c, w->d_pat.alloc(256), "svo pattern");
     if (s) return s;
     if (!w->tiles.empty())
         s = check_hip(c, hipMemcpy(w->d_tiles, w->tiles.data(), w->tiles.size() * sizeof(SvoTile), hipMemcpyHostToDevice),
@@ -124,12 +121,7 @@ rgbd_status svo_alloc(rgbd_ctx* c)
 
 void svo_free(rgbd_ctx* c)
 {
-    SvoWS* w = ws(c);
-    if (!w) return;
-    void* p[] = {w->d_tiles, w->d_pyr, w->d_cells, w->d_box, w->d_cand, w->d_ncand, w->d_pat, w->d_rt_resp, w->d_rt_order};
-    for (void* q : p)
-        if (q) (void)hipFree(q);
-    delete w;
+    delete c->svo;
     c->svo = nullptr;
 }
 
@@ -153,16 +145,16 @@ rgbd_status svo_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d
         if (hs) return hs;
     }
     tk = timer_begin(c, "k_svo_select");
-    RGBD_TRY(c, launch_svo_select(w->d_cells, g, w->d_cand, w->d_ncand, c->d_count, c->d_kps, c->d_err, B, st), "svo_select");
+    RGBD_TRY(c, launch_svo_select(w->d_cells, g, w->d_cand, w->d_ncand, c->out.count, c->out.kps, c->d_err, B, st), "svo_select");
     timer_end(c, tk);
 #ifdef RGBD_PNP_PROFILE
     svo_prof_dump(st);
 #endif
     tk = timer_begin(c, "k_svo_brief");
-    RGBD_TRY(c, launch_svo_brief(w->d_box, c->d_count, c->d_kps, w->d_pat, g, c->d_desc, B, st), "svo_brief");
+    RGBD_TRY(c, launch_svo_brief(w->d_box, c->out.count, c->out.kps, w->d_pat, g, c->out.desc, B, st), "svo_brief");
     timer_end(c, tk);
     tk = timer_begin(c, "k_undistort");
-    RGBD_TRY(c, launch_undistort(d_depth, c->d_count, c->d_cfg, g.kp_cap, c->d_kps, c->d_kun, c->d_xyz, B, st), "undistort");
+    RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, g.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
     timer_end(c, tk);
     c->last_B = B;
     return RGBD_OK;
@@ -247,9 +239,9 @@ rgbd_status rgbd_svo_retain_best(rgbd_ctx* c, const float* resp, int32_t n, int3
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
     SvoWS* w = ws(c);
-    if (!w->d_rt_resp) {
-        s = check_hip(c, hipMalloc((void**)&w->d_rt_resp, (size_t)kSvoSelThreads * kSvoSelMaxE * 4), "retain resp");
-        if (!s) s = check_hip(c, hipMalloc((void**)&w->d_rt_order, ((size_t)kSvoSelThreads * kSvoSelMaxE + 1) * 4), "retain order");
+    if (!w->d_rt_order) {   // the one allocated last
+        s = check_hip(c, w->d_rt_resp.alloc((size_t)kSvoSelThreads * kSvoSelMaxE), "retain resp");
+        if (!s) s = check_hip(c, w->d_rt_order.alloc((size_t)kSvoSelThreads * kSvoSelMaxE + 1), "retain order");
         if (s) return s;
     }
     if (n == 0) { *m = 0; return RGBD_OK; }
