@@ -163,7 +163,10 @@ rgbd_status rgbd_svo_retain_best(rgbd_ctx* ctx, const float* resp, int32_t n, in
                                  int32_t* order, int32_t* m);
 
 /* ------------------------------------------------------------------ matching */
-/* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}. */
+/* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}.
+ * At most 65536 train rows (nt): the kernel's rank key holds the train index in 16 bits.  A larger nt
+ * returns RGBD_ERR_UNSUPPORTED before anything is copied or launched; so does rgbd_match, which runs
+ * rgbd_knn2 first. */
 rgbd_status rgbd_knn2(rgbd_ctx* ctx, const uint8_t* desc_q, int32_t nq, const uint8_t* desc_t, int32_t nt,
                       int32_t* out);
 /* Matcher::match (Features/Matcher.cpp:106-139): ratio test, unique train index (first query

@@ -893,6 +893,8 @@ static rgbd_status ensure_mcap(rgbd_ctx* c, int need, int* cap)
 rgbd_status rgbd_knn2(rgbd_ctx* c, const uint8_t* dq, int32_t nq, const uint8_t* dt, int32_t nt, int32_t* out)
 {
     if (!c || nq < 0 || nt < 0 || (nq > 0 && (!dq || !out)) || (nt > 0 && !dt)) return RGBD_ERR_ARG;
+    // k_knn2m's rank key holds the train index in its low 16 bits
+    if (nt > kKnnMaxTrain) return fail(c, RGBD_ERR_UNSUPPORTED, "knn-2: more than 65536 train rows (16-bit train index in the rank key)");
     if (nq == 0) return RGBD_OK;
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;

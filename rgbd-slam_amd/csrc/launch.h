@@ -26,7 +26,9 @@ hipError_t launch_describe(const uint8_t* pyr, const uint8_t* blur, const int* s
                      hipStream_t st);
 // k_fast's 16-lane emission rank on its own (rgbd_debug_fast_rank16)
 hipError_t launch_debug_rank16(const uint8_t* flags, int rows, uint32_t* slots, uint32_t* counts, hipStream_t st);
-// knn-2 of pairs (qf[p], tf[p]) on the matrix cores (k_knn2m)
+// knn-2 of pairs (qf[p], tf[p]) on the matrix cores (k_knn2m); the rank key holds the train index in 16 bits,
+// so a train set has at most kKnnMaxTrain rows (the caller checks)
+constexpr int kKnnMaxTrain = 65536;
 hipError_t launch_knn2(const uint8_t* desc, const int* counts, const int* qf, const int* tf, int kp_cap, int max_q,
                  int4* out, int npairs, hipStream_t st);
 
