@@ -232,7 +232,9 @@ typedef struct {
 } rgbd_gicp_params;
 
 /* GeneralizedIterativeClosestPoint::align(out, guess): src / tgt M x 3 f32 (M <= 2048, M >= k),
- * guess row-major 4x4.  T = final_transformation_ (identity unless converged). */
+ * guess row-major 4x4.  T = final_transformation_ (identity unless converged).  M < k: PCL computes no
+ * covariances, RGBD_OK and not converged; M > 2048 or k outside [1, 32]: RGBD_ERR_UNSUPPORTED.  Coordinates
+ * must be finite (the tracking chain passes valid-depth inliers; PCL's k-NN orders NaN differently). */
 rgbd_status rgbd_gicp(rgbd_ctx* ctx, const float* src, const float* tgt, int32_t M, const float* guess,
                       const rgbd_gicp_params* prm, float* T, int32_t* converged, int32_t* iterations);
 /* Gicp::compute (Solver/Gicp.cpp:21-35): < 20 pairs -> false; not converged or T.isIdentity() -> false. */
@@ -319,6 +321,12 @@ rgbd_status rgbd_debug_fast_rank16(rgbd_ctx* ctx, const uint8_t* flags, int32_t 
  * the bits of the IEEE expressions (tests/test_gpu_pnp.py: the rotation's and the SVD's operand sets). */
 rgbd_status rgbd_debug_rotation_ops(rgbd_ctx* ctx, const double* x, const double* num, const double* den,
                                     const double* theta, int32_t n, double* sq, double* q, double* t);
+/* rgbd_gicp's covariance stage on its own (csrc/gicp.hip k_gicp_cov, launched with pts as source and as target):
+ * cov[i] = the row-major 3x3 regularised covariance of pts[i] from its k nearest neighbours in pts, for every
+ * point, including those that never get a correspondence and so never reach rgbd_gicp's result.  Checks as
+ * rgbd_gicp: M > 2048 or k outside [1, 32] is RGBD_ERR_UNSUPPORTED; so is M < k (PCL computes no covariances,
+ * rgbd_gicp reports not converged).  Coordinates must be finite (NaN orders differently in PCL's k-NN). */
+rgbd_status rgbd_debug_gicp_cov(rgbd_ctx* ctx, const float* pts, int32_t M, int32_t k, double eps, double* cov /* M x 9 */);
 
 /* Extract + match + PnPRansac over a device-resident chunk (the benchmark path named by the
  * north star; the reference's Tracking uses RansacSE3, see rgbd_track_batch).  For b >= 1:

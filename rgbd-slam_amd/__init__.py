@@ -159,6 +159,7 @@ _SIGS = {
     "rgbd_debug_sort_matches": (_i32, [_vp, _vp, _i32, _i32, _vp]),
     "rgbd_debug_fast_rank16": (_i32, [_vp, _vp, _i32, _vp, _vp]),
     "rgbd_debug_rotation_ops": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "rgbd_debug_gicp_cov": (_i32, [_vp, _vp, _i32, _i32, C.c_double, _vp]),
     "rgbd_pnp_ransac": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(PnpParams), _vp, _vp, _vp, _PI, _PI, _PI]),
     "rgbd_pnp_ransac_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
@@ -653,6 +654,14 @@ class Context:
         self._check(lib().rgbd_gicp_compute(self._h, _ptr(src), _ptr(tgt), len(src), _ptr(guess), C.byref(prm),
                                             _ptr(T), C.byref(ok)), "gicp_compute")
         return bool(ok.value), T.reshape(4, 4)
+
+    def debug_gicp_cov(self, pts, k: int = 20, eps: float = 1e-3) -> np.ndarray:
+        """The covariance stage of gicp() on its own (rgbd_debug_gicp_cov): (M, 3, 3) f64, one matrix per point."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        cov = np.zeros((max(len(pts), 1), 9))
+        self._check(lib().rgbd_debug_gicp_cov(self._h, _ptr(pts), len(pts), int(k), float(eps), _ptr(cov)),
+                    "debug_gicp_cov")
+        return cov[:len(pts)].reshape(-1, 3, 3)
 
     def set_tracking_gicp(self, prm: GicpParams | None):
         self._check(lib().rgbd_set_tracking_gicp(self._h, C.byref(prm) if prm is not None else None),

@@ -620,11 +620,16 @@ hipError_t launch_gicp_align_pairs(const LaneBufs& lb, const LaneCfg& lc, hipStr
     return dispatch(k_gicp_align_pairs, dim3(lc.B), dim3(kAlignThreads), 0, st, lb, lc);
 }
 
+hipError_t launch_gicp_cov(const float* src, const float* tgt, int M, int k, double eps, double* cov, hipStream_t st)
+{
+    return dispatch(k_gicp_cov, dim3((2 * M + kCovG * kCovWaves - 1) / (kCovG * kCovWaves)), dim3(64 * kCovWaves), 0, st, src,
+                    tgt, M, k, eps, cov);
+}
+
 hipError_t launch_gicp(const float* src, const float* tgt, int M, const float* guess, const GicpDevPrm& prm, double* cov,
                  GicpOut* out, double* Mi, hipStream_t st)
 {
-    const hipError_t e = dispatch(k_gicp_cov, dim3((2 * M + kCovG * kCovWaves - 1) / (kCovG * kCovWaves)), dim3(64 * kCovWaves),
-                                  0, st, src, tgt, M, prm.k, prm.gicp_eps, cov);
+    const hipError_t e = launch_gicp_cov(src, tgt, M, prm.k, prm.gicp_eps, cov, st);
     if (e != hipSuccess) return e;
     return dispatch(k_gicp_align, dim3(1), dim3(kAlignThreads), 0, st, src, tgt, M, cov, guess, prm, out, Mi);
 }

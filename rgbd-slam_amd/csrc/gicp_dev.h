@@ -21,5 +21,7 @@ struct GicpOut {
 // covariances of both clouds (cov scratch: 2 M x 9 doubles), then the outer iterations; writes *out
 hipError_t launch_gicp(const float* src, const float* tgt, int M, const float* guess, const GicpDevPrm& prm, double* cov,
                  GicpOut* out, double* Mi, hipStream_t st);   // Mi: M x 9 doubles of scratch
+// the covariance launch of launch_gicp on its own (rgbd_debug_gicp_cov)
+hipError_t launch_gicp_cov(const float* src, const float* tgt, int M, int k, double eps, double* cov, hipStream_t st);
 
 }  // namespace rgbd

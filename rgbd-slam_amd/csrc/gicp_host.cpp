@@ -152,6 +152,26 @@ rgbd_status rgbd_gicp_compute(rgbd_ctx* c, const float* src, const float* tgt, i
     return RGBD_OK;
 }
 
+rgbd_status rgbd_debug_gicp_cov(rgbd_ctx* c, const float* pts, int32_t M, int32_t k, double eps, double* cov)
+{
+    if (!c || !pts || !cov || M < 0) return RGBD_ERR_ARG;
+    if (M > kGicpMaxM) return fail(c, RGBD_ERR_UNSUPPORTED, "more than 2048 points for GICP");
+    if (k < 1 || k > 32) return fail(c, RGBD_ERR_UNSUPPORTED, "GICP k_correspondences must be in [1, 32]");
+    if (M < k) return fail(c, RGBD_ERR_UNSUPPORTED, "fewer points than k_correspondences: PCL computes no covariances");
+    rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
+    if (s) return s;
+    GicpWS* w = nullptr;
+    if ((s = gicp_ws(c, &w))) return s;
+    const hipStream_t st = c->stream;
+    std::memcpy(w->h_pts, pts, (size_t)M * 12);
+    s = check_hip(c, hipMemcpyAsync(w->d_pts, w->h_pts, (size_t)M * 12, hipMemcpyHostToDevice, st), "gicp cov pts");
+    if (s) return s;
+    RGBD_TRY(c, launch_gicp_cov(w->d_pts, w->d_pts, M, k, eps, w->d_cov, st), "gicp_cov");
+    s = check_hip(c, hipMemcpyAsync(cov, w->d_cov, (size_t)M * 9 * sizeof(double), hipMemcpyDeviceToHost, st), "gicp cov out");
+    if (!s) s = check_hip(c, hipStreamSynchronize(st), "sync");
+    return s;
+}
+
 rgbd_status rgbd_set_tracking_gicp(rgbd_ctx* c, const rgbd_gicp_params* prm)
 {
     if (!c) return RGBD_ERR_ARG;

@@ -4,24 +4,7 @@ covariance stage and against known rigid motions.  Parity with PCL's BFGS optimi
 import numpy as np
 import pytest
 
-from gicp_cases import clouds
-
-
-def _np_covariances(P, k=20, eps=1e-3):
-    P32 = P.astype(np.float32)
-    out = []
-    for i in range(len(P32)):
-        d = P32 - P32[i]
-        d2 = (((np.float32(0) + d[:, 0] * d[:, 0]) + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(np.float32)
-        nn = np.lexsort((np.arange(len(P32)), d2))[:k]
-        X = P32[nn]
-        mu = X.astype(np.float64).sum(0) / k
-        # PCL accumulates float products (pt.y * pt.x) into double sums
-        S = np.array([[(X[:, a] * X[:, b]).astype(np.float64).sum() for b in range(3)] for a in range(3)])
-        C = S / k - np.outer(mu, mu)
-        w, V = np.linalg.eigh(C)
-        out.append(V @ np.diag([eps, 1.0, 1.0]) @ V.T)
-    return np.array(out)
+from gicp_cases import clouds, np_covariances
 
 
 @pytest.mark.parametrize("n,seed", [(40, 1), (150, 2)])
@@ -29,7 +12,7 @@ def test_covariances_match_independent(oracle, n, seed):
     P, _, _ = clouds(n, seed)
     ok, C = oracle.gicp_covariances(P)
     assert ok
-    np.testing.assert_allclose(C, _np_covariances(P), atol=1e-9)
+    np.testing.assert_allclose(C, np_covariances(P), atol=1e-9)
 
 
 def test_covariances_refuse_small_cloud(oracle):
