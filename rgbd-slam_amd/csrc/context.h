@@ -111,6 +111,17 @@ void timer_end(rgbd_ctx* c, int tok);
 void timer_flush(rgbd_ctx* c);
 rgbd_status fail(rgbd_ctx* c, rgbd_status code, const std::string& msg);
 rgbd_status check_hip(rgbd_ctx* c, hipError_t e, const char* what);
+// cv::Mat(CV_32F) * cv::Mat on 4x4 row-major matrices: OpenCV's gemm for 32F accumulates each dot product in
+// double in k order (GEMMSingleMul<float,double>) and rounds once
+inline void matmul4(const float* A, const float* B, float* C)
+{
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 4; k++) s += (double)A[4 * i + k] * (double)B[4 * k + j];
+            C[4 * i + j] = (float)s;
+        }
+}
 // c->stream waits for the last extraction when that ran on another stream (api.cpp)
 rgbd_status order_after_extraction(rgbd_ctx* c);
 // a launcher's status (dispatch.h: geometry, LDS opt-in and launch checked) as the entry point's result

@@ -1,5 +1,7 @@
 // lane_replay_dev.h -- the device RansacSE3 loop's sampler and replay (Solver/SolverSE3.cpp:54-125, 135-159),
 // shared by k_lane_match / k_lane_replay (lanes.hip) and the fused replay tail of k_ransac_hyp_lanes (ransac.hip).
+// The rules themselves (sampleMatches, the accept step, the identity fallback's test) are ransac_dev.h's, shared
+// with the host loop (solver.cpp); here are the wave-held generator and the chain's bookkeeping around them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,7 +47,7 @@ struct WaveGlibc {
         return (int32_t)(val >> 1);
     }
     // Random::randomInt(0, M - 1)
-    __device__ int random_int(int M) { return int(((double)next() / ((double)2147483647 + 1.0)) * (double)M); }
+    __device__ int random_int(int M) { return glibc_random_int(next(), M); }
 };
 
 // hypotheses [h0, h1) of lane l: sample ids, their count, cumulative rand() calls (from `calls`); called by a
@@ -59,21 +61,7 @@ __device__ inline void sample_hyps(const LaneBufs& lb, const LaneCfg& lc, int l,
     const bool w0 = (threadIdx.x & 63) == 0;
     for (int h = h0; h < h1; h++) {
         int ids[8];
-        int n = 0, safety = 0;
-        while (n < SS) {
-            int id1 = g.random_int(m);
-            const int id2 = g.random_int(m);
-            calls += 2;
-            if (id1 > id2) id1 = id2;
-            int pos = 0;
-            while (pos < n && ids[pos] < id1) pos++;
-            if (pos == n || ids[pos] != id1) {
-                for (int k = n; k > pos; k--) ids[k] = ids[k - 1];
-                ids[pos] = id1;
-                n++;
-            }
-            if (++safety > 10000) break;
-        }
+        const int n = sample_matches(g, m, SS, ids, calls);
         if (w0) {
             for (int k = 0; k < n; k++) smp[(size_t)h * SS + k] = ids[k];
             scnt[h] = n;
@@ -113,39 +101,25 @@ __device__ inline void lane_replay(const LaneBufs& lb, const LaneCfg& lc, int l,
         if (!c.early) {
             const int H = c.H;
             const int evaluated = phase == 0 ? min(lc.e0, H) : (phase == 1 ? min(lc.e1, H) : H);
-            int validIters = 0;
-            size_t bestN = 0;
+            Se3Loop s;
             int h = 0;
             for (int n = 0; n < lc.iters && (uint32_t)M >= (uint32_t)lc.SS; n++) {
                 if (h >= evaluated) {   // the loop needs a hypothesis not evaluated yet
                     need = true;
                     break;
                 }
-                const HypOut& o = ho[h];
                 h++;
-                if (o.n > 0) {
-                    validIters++;
-                    const size_t nr = (size_t)o.n;
-                    if (o.err <= (double)rmse && nr >= bestN && nr >= lc.minTh) {
-                        rmse = (float)o.err;
-                        bestH = h - 1;
-                        bestN = nr;
-                        if (nr > M * 0.5) n += 10;
-                        if (nr > M * 0.75) n += 10;
-                        if (nr > M * 0.8) break;
-                    }
-                }
+                if (!se3_accept(s, h - 1, ho[h - 1], M, lc.minTh, n)) break;
             }
+            rmse = s.rmse;
+            bestH = s.bestH;
             hused = h;
             if (!need) {
                 // the RNG after the h hypotheses drawn (advanced by the wave below)
                 s_calls = h > 0 ? lb.snap[(size_t)l * lc.H + h - 1] : 0;
-                if (validIters == 0) {   // identity fallback (:105-117)
-                    const HypOut& id = ho[lc.H];
-                    if ((uint32_t)id.n > lc.minTh && id.err < (double)lc.maxMahal) {
-                        bestH = lc.H;
-                        rmse = (float)((double)rmse + id.err);
-                    }
+                if (s.validIters == 0 && se3_identity_ok(ho[lc.H], lc.minTh, lc.maxMahal)) {   // (:105-117)
+                    bestH = lc.H;
+                    rmse = (float)((double)rmse + ho[lc.H].err);
                 }
                 if (bestH >= 0) nin = ho[bestH].n;
                 ok = bestH >= 0 && (uint32_t)nin >= lc.minTh;

@@ -1476,61 +1476,28 @@ __global__ __launch_bounds__(kGatherThreads) void k_match_gather(
 }
 
 // ------------------------------------------------------------------ device sampling and replay
+// (cv::RNG, getSubset, the accept step and RANSACUpdateNumIters: pnp_dev.h)
 namespace {
 
-struct CvRngDev {   // cv::RNG multiply-with-carry
-    uint64_t state;
-    __device__ unsigned next()
-    {
-        state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
-        return (unsigned)state;
-    }
-    __device__ int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
-};
-
-// oracle log_det: + - * / and exact frexp only
-__device__ double log_det(double x)
+// the next n subsets of one problem's cv::RNG stream, into subsets first, first + 1, ... of samples
+__device__ inline void draw_subsets(CvRng& rng, int count, int n, int* __restrict__ samples, size_t first)
 {
-    int e = 0;
-    double m = frexp(x, &e);
-    if (m < 0.70710678118654752440) {
-        m = m * 2.0;
-        e -= 1;
+    for (int i = 0; i < n; i++) {
+        int cur[kPnpModel];
+        get_subset([&]() { return rng.uniform(0, count); }, cur);
+        int* idx = samples + (first + i) * kPnpModel;
+#pragma unroll
+        for (int k = 0; k < kPnpModel; k++) idx[k] = cur[k];
     }
-    const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
-    double t = 1.0 / 23.0;
-    t = t * s2 + 1.0 / 21.0;
-    t = t * s2 + 1.0 / 19.0;
-    t = t * s2 + 1.0 / 17.0;
-    t = t * s2 + 1.0 / 15.0;
-    t = t * s2 + 1.0 / 13.0;
-    t = t * s2 + 1.0 / 11.0;
-    t = t * s2 + 1.0 / 9.0;
-    t = t * s2 + 1.0 / 7.0;
-    t = t * s2 + 1.0 / 5.0;
-    t = t * s2 + 1.0 / 3.0;
-    t = t * s2 + 1.0;
-    const double de = (double)e;
-    return de * 6.93147180559945286227e-01 + (de * 2.31904681384629955842e-17 + 2.0 * s * t);
 }
 
-// oracle update_num_iters (RANSACUpdateNumIters, portable log / power)
-__device__ int update_num_iters(double p, double ep, int modelPoints, int maxIters)
+// the sequential loop over the iterations evaluated so far, [r.iter, r.nh); iteration i's hypothesis is
+// slot slot0 + i - e0 of good / the models
+__device__ inline void replay_chunk(PnpRep& r, const int* __restrict__ good, int slot0, int e0, const PnpPrm& prm)
 {
-    p = p > 0. ? p : 0.;
-    p = p < 1. ? p : 1.;
-    ep = ep > 0. ? ep : 0.;
-    ep = ep < 1. ? ep : 1.;
-    const double DBLMIN = 2.2250738585072014e-308;
-    double num = 1. - p > DBLMIN ? 1. - p : DBLMIN;
-    const double q = 1. - ep;
-    double qm = 1.0;
-    for (int i = 0; i < modelPoints; i++) qm = qm * q;
-    double denom = 1. - qm;
-    if (denom < DBLMIN) return 0;
-    num = log_det(num);
-    denom = log_det(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)rint(num / denom);
+    pnp_replay(r, r.nh, r.count, prm.confidence, [&](int i) { return good[slot0 + i - e0]; },
+               [&](int i) { r.best = slot0 + i - e0; });
+    r.done = r.iter >= r.niters ? 1 : 0;
 }
 
 }  // namespace
@@ -1546,7 +1513,7 @@ __global__ void k_pnp_sample(const PnpProbDev* __restrict__ probs, int P, PnpPrm
     PnpRep r{};
     r.best = -1;
     r.count = count;
-    CvRngDev rng{~0ull};
+    CvRng rng(~0ull);
     int nh = 0;
     if (count >= minc) {
         if (count == kPnpModel) {
@@ -1556,23 +1523,7 @@ __global__ void k_pnp_sample(const PnpProbDev* __restrict__ probs, int P, PnpPrm
         } else {
             const int iters = prm.iterations > 1 ? prm.iterations : 1;
             nh = K0 < iters ? K0 : iters;
-            for (int i = 0; i < nh; i++) {
-                // the subset lives in registers while it is drawn (the duplicate test reads it)
-                int cur[kPnpModel];
-#pragma unroll
-                for (int k = 0; k < kPnpModel; k++) {
-                    for (;;) {
-                        const int v = rng.uniform(0, count);
-                        bool dup = false;
-#pragma unroll
-                        for (int j = 0; j < k; j++) dup |= cur[j] == v;
-                        if (!dup) { cur[k] = v; break; }
-                    }
-                }
-                int* idx = samples + ((size_t)p * K0 + i) * kPnpModel;
-#pragma unroll
-                for (int k = 0; k < kPnpModel; k++) idx[k] = cur[k];
-            }
+            draw_subsets(rng, count, nh, samples, (size_t)p * K0);
         }
     }
     for (int i = 0; i < K0; i++) hyp_prob[(size_t)p * K0 + i] = i < nh ? p : -1;
@@ -1604,23 +1555,14 @@ __global__ void k_pnp_replay(const int* __restrict__ good, int P, PnpPrm prm, Pn
         r.done = 1;
     } else {
         r.niters = prm.iterations > 1 ? prm.iterations : 1;
-        while (r.iter < r.niters && r.iter < r.nh) {
-            const int g = good[base + r.iter];
-            if (g >= 0 && g > (r.maxGood > kPnpModel - 1 ? r.maxGood : kPnpModel - 1)) {
-                r.maxGood = g;
-                r.best = base + r.iter;
-                r.niters = update_num_iters(prm.confidence, (double)(r.count - g) / r.count, kPnpModel, r.niters);
-            }
-            r.iter++;
-        }
-        r.done = r.iter >= r.niters ? 1 : 0;
+        replay_chunk(r, good, base, 0, prm);
     }
     rep[p] = r;
     best[p] = (r.done && r.best >= 0 && r.maxGood > 0) ? r.best : -1;
     best[P + p] = r.force_all;
 }
 
-// the second chunk's subsets, continuing each unfinished problem's cv::RNG stream (getSubset as k_pnp_sample)
+// the second chunk's subsets, continuing each unfinished problem's cv::RNG stream
 __global__ void k_pnp_sample2(int P, PnpPrm prm, int* __restrict__ samples, int* __restrict__ hyp_prob,
                               PnpRep* __restrict__ rep)
 {
@@ -1632,23 +1574,9 @@ __global__ void k_pnp_sample2(int P, PnpPrm prm, int* __restrict__ samples, int*
     if (!r.done && !r.force_all && r.nh > 0) {   // the replay consumed every drawn subset: iter == nh < niters
         k = r.niters - r.nh;
         k = k < K1 ? k : K1;
-        CvRngDev rng{r.rng};
-        for (int i = 0; i < k; i++) {
-            int cur[kPnpModel];
-#pragma unroll
-            for (int q = 0; q < kPnpModel; q++) {
-                for (;;) {
-                    const int v = rng.uniform(0, r.count);
-                    bool dup = false;
-#pragma unroll
-                    for (int j = 0; j < q; j++) dup |= cur[j] == v;
-                    if (!dup) { cur[q] = v; break; }
-                }
-            }
-            int* idx = samples + ((size_t)p * K1 + i) * kPnpModel;
-#pragma unroll
-            for (int q = 0; q < kPnpModel; q++) idx[q] = cur[q];
-        }
+        CvRng rng;
+        rng.state = r.rng;
+        draw_subsets(rng, r.count, k, samples, (size_t)p * K1);
         r.rng = rng.state;
     }
     for (int i = 0; i < K1; i++) hyp_prob[(size_t)p * K1 + i] = i < k ? p : -1;
@@ -1664,18 +1592,9 @@ __global__ void k_pnp_replay2(const int* __restrict__ good, int h01, int P, PnpP
     if (p >= P) return;
     PnpRep r = rep[p];
     if (r.nh2 > 0) {
-        const int base = h01 + p * prm.chunk2, e0 = r.nh;
+        const int e0 = r.nh;
         r.nh += r.nh2;
-        while (r.iter < r.niters && r.iter < r.nh) {
-            const int g = good[base + r.iter - e0];
-            if (g >= 0 && g > (r.maxGood > kPnpModel - 1 ? r.maxGood : kPnpModel - 1)) {
-                r.maxGood = g;
-                r.best = base + r.iter - e0;
-                r.niters = update_num_iters(prm.confidence, (double)(r.count - g) / r.count, kPnpModel, r.niters);
-            }
-            r.iter++;
-        }
-        r.done = r.iter >= r.niters ? 1 : 0;
+        replay_chunk(r, good, h01 + p * prm.chunk2, e0, prm);
         r.nh2 = 0;
     }
     rep[p] = r;
@@ -1876,9 +1795,11 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_pnp_chain(
         const bool force = count == kPnpModel && count >= minc;   // runKernel once, every point an inlier
         // the cv::RNG((uint64)-1) stream of every call is the same: rngtab[j] = its (j + 1)-th raw output (host
         // table), rng_end = the state after the table (draws past it continue sequentially on wave 0)
-        CvRngDev rng{rng_end};
-        int maxGood = 0, iter = 0, ev = 0, have = 0, pos = 0;
-        int niters = count >= minc ? (force ? 1 : (prm.iterations > 1 ? prm.iterations : 1)) : 0;
+        CvRng rng;
+        rng.state = rng_end;
+        int ev = 0, pos = 0;
+        // run.best: the pass slot of the last accepted model (its copy is in L.best), -1 while there is none
+        PnpLoop run{-1, 0, 0, count >= minc ? (force ? 1 : (prm.iterations > 1 ? prm.iterations : 1)) : 0};
         if (tid == 0) L.pos = 0;
         __syncthreads();
         for (;;) {
@@ -1891,7 +1812,7 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_pnp_chain(
             __syncthreads();
             // wave 0 keeps the RANSACPointSetRegistrator::run state (every lane the same values)
             if (wave == 0) {
-                int k = iter < niters ? niters - ev : 0;
+                int k = run.iter < run.niters ? run.niters - ev : 0;
                 k = k < kChainHyp ? k : kChainHyp;
                 if (force) {
                     if (lane < kPnpModel) L.samples[lane] = lane;
@@ -1925,22 +1846,16 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_pnp_chain(
                             if (I == k) break;
                         }
                         int cur[kPnpModel];
-#pragma unroll
-                        for (int q = 0; q < kPnpModel; q++) {
-                            for (;;) {
-                                const int at = p0 + o;
-                                int v;
-                                if (at < ntab)
-                                    v = o < kChainThreads ? (int)L.vals[o] : (int)(rngtab[at] % (unsigned)count);
-                                else
-                                    v = (int)(rng.next() % (unsigned)count);
-                                o++;
-                                bool dup = false;
-#pragma unroll
-                                for (int j = 0; j < q; j++) dup |= cur[j] == v;
-                                if (!dup) { cur[q] = v; break; }
-                            }
-                        }
+                        get_subset([&]() {
+                            const int at = p0 + o;
+                            int v;
+                            if (at < ntab)
+                                v = o < kChainThreads ? (int)L.vals[o] : (int)(rngtab[at] % (unsigned)count);
+                            else
+                                v = (int)(rng.next() % (unsigned)count);
+                            o++;
+                            return v;
+                        }, cur);
                         if (lane == 0)
 #pragma unroll
                             for (int q = 0; q < kPnpModel; q++) L.samples[I * kPnpModel + q] = cur[q];
@@ -1965,30 +1880,24 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_pnp_chain(
             if (wave == 0) {   // the sequential replay of this pass (accept, RANSACUpdateNumIters)
                 const int e0 = ev;
                 ev += kk;
+                const auto keep = [&](int i) {   // the accepted model, kept across passes
+                    run.best = i - e0;
+                    if (lane < 12) L.best[lane] = (&L.models[i - e0].R[0])[lane];
+                };
                 if (force) {
                     if (L.good[0] >= 0) {
-                        maxGood = count;
-                        have = 1;
-                        if (lane < 12) L.best[lane] = (&L.models[0].R[0])[lane];
+                        run.maxGood = count;
+                        keep(e0);
                     }
-                    niters = 0;
+                    run.niters = 0;
                 } else {
-                    while (iter < niters && iter < ev) {
-                        const int gd = L.good[iter - e0];
-                        if (gd >= 0 && gd > (maxGood > kPnpModel - 1 ? maxGood : kPnpModel - 1)) {
-                            maxGood = gd;
-                            have = 1;
-                            if (lane < 12) L.best[lane] = (&L.models[iter - e0].R[0])[lane];
-                            niters = update_num_iters(prm.confidence, (double)(count - gd) / count, kPnpModel, niters);
-                        }
-                        iter++;
-                    }
+                    pnp_replay(run, ev, count, prm.confidence, [&](int i) { return L.good[i - e0]; }, keep);
                 }
             }
             CHAIN_T(a3);
             CHAIN_ADD(3, a2, a3);
         }
-        if (tid == 0) L.ok = have && maxGood > 0;
+        if (tid == 0) L.ok = run.best >= 0 && run.maxGood > 0;
         __syncthreads();
         const bool ok = L.ok != 0;
         CHAIN_T(t2);
@@ -2006,8 +1915,8 @@ __global__ __launch_bounds__(kChainThreads, 1) void k_pnp_chain(
             PnpChainRes r{};
             r.count = count;
             r.ok = ok ? 1 : 0;
-            r.n_inliers = ok ? maxGood : 0;
-            r.iters = iter;
+            r.n_inliers = ok ? run.maxGood : 0;
+            r.iters = run.iter;
             res[p] = r;
             probs[p] = PnpProbDev{(int)po, count};
             best[p] = ok ? p : -1;   // k_pnp_refine's inputs

@@ -1,6 +1,7 @@
 // pnp_dev.h -- PnPRansac kernels interface (host <-> device).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace rgbd {
@@ -22,9 +23,12 @@ struct PnpModel {                  // [R | t], x_cam = R X + t, row-major R
     double t[3];
 };
 
-struct PnpRep {                    // RANSAC replay state of one problem after the device chunks
-    int32_t best;                  // global hypothesis slot of the best model, -1 if none
+struct PnpLoop {                   // RANSACPointSetRegistrator::run's loop state (pnp_replay below)
+    int32_t best;                  // the caller's name for the best model (a hypothesis slot), -1 if none
     int32_t maxGood, iter, niters;
+};
+
+struct PnpRep : PnpLoop {          // RANSAC replay state of one problem after the device chunks (best: global slot)
     int32_t done;                  // 1: the replay reached niters (or the problem is inactive)
     int32_t count, force_all, nh;  // points, count == 5 path, hypotheses drawn (both chunks)
     int32_t nh2, pad_;             // hypotheses of the second chunk
@@ -39,6 +43,106 @@ struct PnpPrm {                    // solvePnPRansac arguments as the device rep
     int32_t iterations, min_matches, chunk, chunk2;   // hypotheses per problem of the first / second device chunk
     double confidence;
 };
+
+// ------------------------------------------------------------------ the loop rules of cv::solvePnPRansac
+// RANSACPointSetRegistrator::run (OpenCV 3.4 ptsetreg.cpp) as oracle/orc_pnp.cpp defines it, written once for
+// the host (pnp_host.cpp) and the kernels (pnp.hip): both are compiled with -ffp-contract=off -fno-fast-math,
+// so one definition is one arithmetic.  tests/ransac_loop_check.cpp holds these to the oracle on the CPU.
+
+struct CvRng {                     // cv::RNG: multiply-with-carry; solvePnPRansac seeds it with (uint64)-1
+    uint64_t state;
+    __host__ __device__ explicit CvRng(uint64_t seed = ~0ull) : state(seed ? seed : 0xffffffffull) {}
+    __host__ __device__ unsigned next()
+    {
+        state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
+        return (unsigned)state;
+    }
+    __host__ __device__ int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
+};
+
+// the oracle's log_det: a portable log from + - * / and exact frexp only
+__host__ __device__ inline double log_det(double x)
+{
+    int e = 0;
+    double m = frexp(x, &e);
+    if (m < 0.70710678118654752440) {
+        m = m * 2.0;
+        e -= 1;
+    }
+    const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
+    double t = 1.0 / 23.0;
+    t = t * s2 + 1.0 / 21.0;
+    t = t * s2 + 1.0 / 19.0;
+    t = t * s2 + 1.0 / 17.0;
+    t = t * s2 + 1.0 / 15.0;
+    t = t * s2 + 1.0 / 13.0;
+    t = t * s2 + 1.0 / 11.0;
+    t = t * s2 + 1.0 / 9.0;
+    t = t * s2 + 1.0 / 7.0;
+    t = t * s2 + 1.0 / 5.0;
+    t = t * s2 + 1.0 / 3.0;
+    t = t * s2 + 1.0;
+    const double de = (double)e;
+    return de * 6.93147180559945286227e-01 + (de * 2.31904681384629955842e-17 + 2.0 * s * t);
+}
+
+// RANSACUpdateNumIters with the portable log / power (the oracle's update_num_iters)
+__host__ __device__ inline int update_num_iters(double p, double ep, int modelPoints, int maxIters)
+{
+    p = p > 0. ? p : 0.;
+    p = p < 1. ? p : 1.;
+    ep = ep > 0. ? ep : 0.;
+    ep = ep < 1. ? ep : 1.;
+    const double DBLMIN = 2.2250738585072014e-308;
+    double num = 1. - p > DBLMIN ? 1. - p : DBLMIN;
+    const double q = 1. - ep;
+    double qm = 1.0;
+    for (int i = 0; i < modelPoints; i++) qm = qm * q;
+    double denom = 1. - qm;
+    if (denom < DBLMIN) return 0;
+    num = log_det(num);
+    denom = log_det(denom);
+    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)rint(num / denom);
+}
+
+// getSubset with an always-true checkSubset: kPnpModel distinct indices, a repeated one drawn again.
+// draw() = the stream's next uniform(0, count) value.  cur is the caller's array: registers in a kernel
+// (the duplicate test reads it while the subset is drawn).
+template <class Draw>
+__host__ __device__ inline void get_subset(Draw draw, int* cur)
+{
+#pragma unroll
+    for (int k = 0; k < kPnpModel; k++) {
+        for (;;) {
+            const int v = draw();
+            bool dup = false;
+#pragma unroll
+            for (int j = 0; j < k; j++) dup |= cur[j] == v;
+            if (!dup) { cur[k] = v; break; }
+        }
+    }
+}
+
+// one iteration's accept step: g = the hypothesis' inlier count, or -1 when the minimal solver found no
+// model.  accepted(i) is told that iteration i's model is the new best one (the caller records which it was).
+template <class Accepted>
+__host__ __device__ inline void pnp_accept(PnpLoop& s, int g, int count, double confidence, Accepted accepted)
+{
+    if (g >= 0 && g > (s.maxGood > kPnpModel - 1 ? s.maxGood : kPnpModel - 1)) {
+        s.maxGood = g;
+        accepted(s.iter);
+        s.niters = update_num_iters(confidence, (double)(count - g) / count, kPnpModel, s.niters);
+    }
+    s.iter++;
+}
+
+// the loop over iterations [s.iter, min(s.niters, evaluated)): good(i) = iteration i's inlier count
+template <class Good, class Accepted>
+__host__ __device__ inline void pnp_replay(PnpLoop& s, int evaluated, int count, double confidence, Good good,
+                                           Accepted accepted)
+{
+    while (s.iter < s.niters && s.iter < evaluated) pnp_accept(s, good(s.iter), count, confidence, accepted);
+}
 
 // one thread per problem: the first `chunk` subsets of the cv::RNG((uint64)-1) stream (one fixed
 // subset for count == 5), hyp_prob[p * chunk + i] = p or -1, rep[p].{count, force_all, nh, rng}

@@ -4,14 +4,13 @@
 // cv::solvePnPRansac (called at Solver/PnPRansac.cpp:39) is RANSACPointSetRegistrator::run with a
 // fresh cv::RNG((uint64)-1): the subset drawn at iteration i depends only on the point count.  So
 // the host draws the subsets of a chunk of iterations, k_pnp_hyp evaluates all of them (and all
-// problems of a batch) in one launch, and the host replays the loop in order:
-//     goodCount > max(maxGood, modelPoints - 1)  ->  best, niters = RANSACUpdateNumIters(...)
+// problems of a batch) in one launch, and the host replays the loop in order (the loop's rules -- cv::RNG,
+// getSubset, the accept step, RANSACUpdateNumIters -- are pnp_dev.h's, shared with the kernels),
 // drawing further chunks only while the replay has not reached niters.  k_pnp_refine then refines
 // every problem's best model on its inliers.  Semantics: oracle/orc_pnp.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <utility>
@@ -26,76 +25,6 @@ using namespace rgbd;
 namespace rgbd {
 
 namespace {
-
-// cv::RNG: multiply-with-carry, state = (uint64)-1 for RANSACPointSetRegistrator
-struct CvRng {
-    uint64_t state;
-    explicit CvRng(uint64_t s = ~0ull) : state(s ? s : 0xffffffffull) {}
-    unsigned next()
-    {
-        state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
-        return (unsigned)state;
-    }
-    int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
-};
-
-// oracle log_det (portable log from + - * / and exact frexp; the device replay computes the same)
-double log_det(double x)
-{
-    int e = 0;
-    double m = std::frexp(x, &e);
-    if (m < 0.70710678118654752440) {
-        m = m * 2.0;
-        e -= 1;
-    }
-    const double s = (m - 1.0) / (m + 1.0), s2 = s * s;
-    double t = 1.0 / 23.0;
-    t = t * s2 + 1.0 / 21.0;
-    t = t * s2 + 1.0 / 19.0;
-    t = t * s2 + 1.0 / 17.0;
-    t = t * s2 + 1.0 / 15.0;
-    t = t * s2 + 1.0 / 13.0;
-    t = t * s2 + 1.0 / 11.0;
-    t = t * s2 + 1.0 / 9.0;
-    t = t * s2 + 1.0 / 7.0;
-    t = t * s2 + 1.0 / 5.0;
-    t = t * s2 + 1.0 / 3.0;
-    t = t * s2 + 1.0;
-    const double de = (double)e;
-    return de * 6.93147180559945286227e-01 + (de * 2.31904681384629955842e-17 + 2.0 * s * t);
-}
-
-// RANSACUpdateNumIters (OpenCV 3.4 ptsetreg.cpp), portable log / power (oracle update_num_iters)
-int update_num_iters(double p, double ep, int modelPoints, int maxIters)
-{
-    p = p > 0. ? p : 0.;
-    p = p < 1. ? p : 1.;
-    ep = ep > 0. ? ep : 0.;
-    ep = ep < 1. ? ep : 1.;
-    double num = 1. - p > DBL_MIN ? 1. - p : DBL_MIN;
-    const double q = 1. - ep;
-    double qm = 1.0;
-    for (int i = 0; i < modelPoints; i++) qm = qm * q;
-    double denom = 1. - qm;
-    if (denom < DBL_MIN) return 0;
-    num = log_det(num);
-    denom = log_det(denom);
-    return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)std::nearbyint(num / denom);
-}
-
-// RANSACPointSetRegistrator::getSubset with an always-true checkSubset: 5 distinct indices
-void draw_subset(CvRng& rng, int count, int* idx)
-{
-    for (int i = 0; i < kPnpModel; i++) {
-        for (;;) {
-            const int v = rng.uniform(0, count);
-            int j;
-            for (j = 0; j < i; j++)
-                if (idx[j] == v) break;
-            if (j == i) { idx[i] = v; break; }
-        }
-    }
-}
 
 // iterations per problem evaluated on the device, in two chunks: every problem's first K0 subsets, then
 // for the problems whose replay has not reached niters the next K1 (k_pnp_sample2 / k_pnp_replay2, no
@@ -148,6 +77,14 @@ struct PnpWS {
 };
 
 static hipStream_t ws_stream(const rgbd_ctx* c, const PnpWS* w) { return w->st ? w->st : c->stream; }
+
+// the squared reprojection error the inlier tests compare with
+static float reproj_thr(const rgbd_pnp_params& prm)
+{
+    return (float)((double)prm.reprojection_error * (double)prm.reprojection_error);
+}
+
+static PnpCam ctx_cam(const rgbd_ctx* c) { return PnpCam{c->cam.fx, c->cam.fy, c->cam.cx, c->cam.cy}; }
 
 // submit / collect tracking: kPipeDepth workspaces used in turn, submissions collected in order.
 // A submission's PnPRansac solve is launched (on the solve stream) by the NEXT submission right after
@@ -293,7 +230,7 @@ static rgbd_status pnp_sample_launch(rgbd_ctx* c, PnpWS* w, int P, const rgbd_pn
 static rgbd_status pnp_launch(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, const rgbd_pnp_params& prm)
 {
     const hipStream_t st = ws_stream(c, w);
-    const float thr = (float)((double)prm.reprojection_error * (double)prm.reprojection_error);
+    const float thr = reproj_thr(prm);
     rgbd_status s = RGBD_OK;
     if (!w->sampled && (s = pnp_sample_launch(c, w, P, prm, st))) return s;
     w->sampled = false;
@@ -336,7 +273,7 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
                               PnpResult* res)
 {
     const hipStream_t st = ws_stream(c, w);
-    const float thr = (float)((double)prm.reprojection_error * (double)prm.reprojection_error);
+    const float thr = reproj_thr(prm);
     const int H0 = w->h01;   // hypothesis slots of the two device chunks
     rgbd_status s = check_hip(c, hipEventSynchronize(w->ev), "pnp wait");
     if (s) return s;
@@ -363,7 +300,8 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
 
     // ---- host continuation (solvePnPRansac still iterating after the first chunk)
     struct Run {
-        int p = 0, count = 0, niters = 0, iter = 0, evaluated = 0, maxGood = 0, best = -1, chunk = 0;
+        int p = 0, count = 0, evaluated = 0, chunk = 0;
+        PnpLoop s{-1, 0, 0, 0};   // best: a global hypothesis slot
         CvRng rng;
         std::vector<int> slot;   // global hypothesis slot of each evaluated iteration >= K0 ... (by index)
     };
@@ -373,11 +311,8 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
         Run u;
         u.p = p;
         u.count = r.count;
-        u.niters = r.niters;
-        u.iter = r.iter;
+        u.s = r;
         u.evaluated = r.nh;
-        u.maxGood = r.maxGood;
-        u.best = r.best;
         u.chunk = 2 * w->k1;
         u.rng.state = r.rng;
         run.push_back(u);
@@ -387,7 +322,7 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
     while (nactive > 0) {
         int H = 0;
         for (const Run& u : run)
-            if (u.iter < u.niters) H += std::min(u.chunk, u.niters - u.evaluated);
+            if (u.s.iter < u.s.niters) H += std::min(u.chunk, u.s.niters - u.evaluated);
         s = check_hip(c, w->h_hprob.reserve((size_t)H), "pnp h hprob");
         if (!s) s = check_hip(c, w->h_samples.reserve((size_t)H * kPnpModel), "pnp h samples");
         if (!s) s = check_hip(c, w->h_good.reserve((size_t)H), "pnp h good");
@@ -397,12 +332,12 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
         if (s) return s;
         int h = 0;
         for (Run& u : run) {
-            if (u.iter >= u.niters) continue;
-            const int k = std::min(u.chunk, u.niters - u.evaluated);
+            if (u.s.iter >= u.s.niters) continue;
+            const int k = std::min(u.chunk, u.s.niters - u.evaluated);
             u.slot.assign(k, 0);
             for (int i = 0; i < k; i++, h++) {
                 w->h_hprob[h] = u.p;
-                draw_subset(u.rng, u.count, &w->h_samples[(size_t)h * kPnpModel]);
+                get_subset([&]() { return u.rng.uniform(0, u.count); }, &w->h_samples[(size_t)h * kPnpModel]);
                 u.slot[i] = Htot + h;
             }
             u.chunk *= 2;
@@ -418,30 +353,23 @@ static rgbd_status pnp_finish(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, c
         if (!s) s = check_hip(c, hipStreamSynchronize(st), "sync");
         if (s) return s;
         for (Run& u : run) {   // replay (RANSACPointSetRegistrator::run)
-            if (u.iter >= u.niters) continue;
+            if (u.s.iter >= u.s.niters) continue;
             const int first = u.evaluated;
             u.evaluated += (int)u.slot.size();
-            while (u.iter < u.niters && u.iter < u.evaluated) {
-                const int slot = u.slot[u.iter - first];
-                const int g = w->h_good[slot - Htot];
-                if (g >= 0 && g > std::max(u.maxGood, kPnpModel - 1)) {
-                    u.maxGood = g;
-                    u.best = slot;
-                    u.niters = update_num_iters(prm.confidence, (double)(u.count - g) / u.count, kPnpModel, u.niters);
-                }
-                u.iter++;
-            }
-            if (u.iter >= u.niters) nactive--;
+            pnp_replay(u.s, u.evaluated, u.count, prm.confidence,
+                       [&](int i) { return w->h_good[u.slot[i - first] - Htot]; },
+                       [&](int i) { u.s.best = u.slot[i - first]; });
+            if (u.s.iter >= u.s.niters) nactive--;
         }
         Htot += H;
     }
     for (int p = 0; p < P; p++) w->h_best[p] = -1, w->h_best[P + p] = 0;
     for (const Run& u : run) {
-        const bool ok = u.best >= 0 && u.maxGood > 0;
-        w->h_best[u.p] = ok ? u.best : -1;
+        const bool ok = u.s.best >= 0 && u.s.maxGood > 0;
+        w->h_best[u.p] = ok ? u.s.best : -1;
         res[u.p].ok = ok ? 1 : 0;
-        res[u.p].n_inliers = ok ? u.maxGood : 0;
-        res[u.p].iters = u.iter;
+        res[u.p].n_inliers = ok ? u.s.maxGood : 0;
+        res[u.p].iters = u.s.iter;
     }
     s = check_hip(c, hipMemcpyAsync(w->d_best, w->h_best, (size_t)2 * P * 4, hipMemcpyHostToDevice, st), "best");
     if (s) return s;
@@ -463,16 +391,6 @@ static rgbd_status pnp_solve(rgbd_ctx* c, PnpWS* w, int P, const PnpCam& cam, co
 {
     rgbd_status s = pnp_launch(c, w, P, cam, prm);
     return s ? s : pnp_finish(c, w, P, cam, prm, res);
-}
-
-static void matmul4(const float* A, const float* B, float* C)   // cv::Mat 32F gemm: double accumulation
-{
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double s = 0.0;
-            for (int k = 0; k < 4; k++) s += (double)A[4 * i + k] * (double)B[4 * k + j];
-            C[4 * i + j] = (float)s;
-        }
 }
 
 }  // namespace rgbd
@@ -635,7 +553,7 @@ static rgbd_status pnp_solve_launch(rgbd_ctx* c, PnpWS* w, int P, const rgbd_pnp
         if (!s && also) s = check_hip(c, hipStreamWaitEvent(w->st, also, 0), "pnp launch-stream wait");
         if (s) return s;
     }
-    const PnpCam cam{c->cam.fx, c->cam.fy, c->cam.cx, c->cam.cy};
+    const PnpCam cam = ctx_cam(c);
     return pnp_launch(c, w, P, cam, prm);
 }
 
@@ -681,8 +599,8 @@ static rgbd_status flag_chain_launch(rgbd_ctx* c, PnpWS* w, const OutSet& o, int
     s = check_hip(c, hipMemcpyAsync(w->d_seg, w->h_seg, (size_t)(S + 1) * 4, hipMemcpyHostToDevice, st), "flag runs");
     if (!s) s = check_hip(c, hipMemsetAsync(w->d_flags, 0, (size_t)B * K, st), "flags clear");   // fresh frames
     if (s) return s;
-    const PnpCam cam{c->cam.fx, c->cam.fy, c->cam.cx, c->cam.cy};
-    const float thr = (float)((double)prm.reprojection_error * (double)prm.reprojection_error);
+    const PnpCam cam = ctx_cam(c);
+    const float thr = reproj_thr(prm);
     const PnpPrm dp{prm.iterations, prm.min_matches, 0, 0, prm.confidence};
     const int tk = timer_begin(c, "k_pnp_chain", st);
     RGBD_TRY(c, launch_pnp_chain(o.knn, o.count, o.xyz, o.kun, K, nnratio, w->d_seg, S, cam, thr, dp, w->d_p3, w->d_p2, w->d_mq,
@@ -733,7 +651,7 @@ static rgbd_status track_collect(rgbd_ctx* c, PnpWS* w, int B, float nnratio, co
     status[0] = 1;
     if (n_inliers) n_inliers[0] = 0;
     if (n_matches) n_matches[0] = 0;
-    const PnpCam cam{c->cam.fx, c->cam.fy, c->cam.cx, c->cam.cy};
+    const PnpCam cam = ctx_cam(c);
     std::vector<PnpResult> res(std::max(P, 1));
     rgbd_status s = RGBD_OK;
     if (P == 0)

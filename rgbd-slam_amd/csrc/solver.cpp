@@ -5,9 +5,10 @@
 //           reference, unstable, ties decided by its comparison sequence), glibc-rand sample draws
 //           (sampleMatches :135-159) for every iteration that may run, sticky depth covariance (:282)
 //   device: k_ransac_hyp -- every iteration's refinement chain (:58-86) in parallel
-//   host:   replay of the sequential accept / n += 10 / break logic (:88-102), the identity
-//           fallback (:105-117), inlier flags (:119-122), and the RNG advanced by exactly the
-//           samples the reference would have drawn.
+//   host:   replay of the sequential loop (:88-102) and the identity fallback (:105-117) by the rules of
+//           ransac_dev.h (sample_matches, se3_accept, se3_identity_ok: one definition, shared with the
+//           device loop in lane_replay_dev.h), inlier flags (:119-122), and the RNG advanced by exactly
+//           the samples the reference would have drawn.
 // Tracking::visualOdometry (System/Tracking.cpp:121-163) over a device-resident batch runs entirely on the
 // device (lanes_host.cpp); the host composes the poses and Tracking::track's bookkeeping from its results.
 #include <hip/hip_runtime.h>
@@ -87,33 +88,11 @@ static int32_t rng_next(rgbd_rng* st)
     return result;
 }
 
-// Random::randomInt, System/Random.cpp:16-20
-static int random_int(rgbd_rng* st, int mn, int mx)
-{
-    const int d = mx - mn + 1;
-    return int(((double)rng_next(st) / ((double)2147483647 + 1.0)) * d) + mn;
-}
-
-// RansacSE3::sampleMatches (:135-159): ids in std::set order (ascending, distinct)
-static int sample_ids(rgbd_rng* st, int M, int SS, int* ids)
-{
-    int n = 0;
-    int safety = 0;
-    while (n < SS && M >= SS) {
-        int id1 = random_int(st, 0, M - 1);
-        const int id2 = random_int(st, 0, M - 1);
-        if (id1 > id2) id1 = id2;
-        int pos = 0;
-        while (pos < n && ids[pos] < id1) pos++;
-        if (pos == n || ids[pos] != id1) {
-            for (int k = n; k > pos; k--) ids[k] = ids[k - 1];
-            ids[pos] = id1;
-            n++;
-        }
-        if (++safety > 10000) break;
-    }
-    return n;
-}
+// the generator sample_matches draws from (ransac_dev.h): Random::randomInt(0, M - 1) on the host's state
+struct HostGlibc {
+    rgbd_rng* st;
+    int random_int(int M) { return glibc_random_int(rng_next(st), M); }
+};
 
 static const int kFirstChunk = 24;   // hypotheses evaluated before the first replay
 
@@ -177,9 +156,11 @@ rgbd_status ransac_se3(rgbd_ctx* c, const float* xyz1, const float* xyz2, const 
     w->after.resize(std::max(H, 1));
     const int SSd = std::max(SS, 1);
     int drawn = 0;
+    HostGlibc gen{&r};
+    int calls = 0;   // the device loop's rand() count; the host keeps the state after each hypothesis instead
     auto draw_to = [&](int hend) {
         for (; drawn < hend; drawn++) {
-            w->scount()[drawn] = sample_ids(&r, M, SS, &w->samples()[(size_t)drawn * SSd]);
+            w->scount()[drawn] = sample_matches(gen, M, SS, &w->samples()[(size_t)drawn * SSd], calls);
             w->after[drawn] = r;
         }
     };
@@ -237,44 +218,28 @@ rgbd_status ransac_se3(rgbd_ctx* c, const float* xyz1, const float* xyz2, const 
         std::copy(&w->masks()[(size_t)h1 * w->MWcap], &w->masks()[(size_t)h1 * w->MWcap] + MW, identMask.begin());
     }
     // replay (:56-103)
-    int validIters = 0;
-    float rmse = 1e6f;
-    int bestH = -1;
-    size_t bestN = 0;
+    Se3Loop loop;
     int h = 0;
     for (int n = 0; n < prm.iterations && (uint32_t)M >= prm.sample_size; n++) {
         if (h >= evaluated) {
             if ((s = run_chunk(evaluated, H))) return s;
             evaluated = H;
         }
-        const HypOut& o = w->out()[h];
         h++;
-        if (o.n > 0) {
-            validIters++;
-            const size_t nr = (size_t)o.n;
-            if (o.err <= (double)rmse && nr >= bestN && nr >= prm.min_inlier_th) {
-                rmse = (float)o.err;
-                bestH = h - 1;
-                bestN = nr;
-                if (nr > used.size() * 0.5) n += 10;
-                if (nr > used.size() * 0.75) n += 10;
-                if (nr > used.size() * 0.8) break;
-            }
-        }
+        if (!se3_accept(loop, h - 1, w->out()[h - 1], M, prm.min_inlier_th, n)) break;
     }
+    float rmse = loop.rmse;
+    const int bestH = loop.bestH;
     *rng = (h > 0) ? w->after[h - 1] : snapshot;
     const uint32_t* mask = nullptr;
     if (bestH >= 0) {
         std::memcpy(R.T, w->out()[bestH].T, sizeof(R.T));
         mask = &w->masks()[(size_t)bestH * w->MWcap];
     }
-    if (validIters == 0) {   // identity fallback (:105-117)
-        if ((uint32_t)ident.n > prm.min_inlier_th && ident.err < (double)prm.max_mahalanobis) {
-            for (int i = 0; i < 16; i++) R.T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-            mask = identMask.data();
-            rmse = (float)((double)rmse + ident.err);
-            bestN = (size_t)ident.n;
-        }
+    if (loop.validIters == 0 && se3_identity_ok(ident, prm.min_inlier_th, prm.max_mahalanobis)) {   // (:105-117)
+        for (int i = 0; i < 16; i++) R.T[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        mask = identMask.data();
+        rmse = (float)((double)rmse + ident.err);
     }
     R.rmse = rmse;
     if (mask)
@@ -284,18 +249,6 @@ rgbd_status ransac_se3(rgbd_ctx* c, const float* xyz1, const float* xyz2, const 
     if (R.ok && update_f2 && flags2)
         for (const rgbd_dmatch& mm : R.inliers) flags2[mm.trainIdx] = 0;
     return RGBD_OK;
-}
-
-// cv::Mat(CV_32F) * cv::Mat: OpenCV gemm for 32F accumulates each dot product in double in k order
-// (GEMMSingleMul<float,double>) and rounds once.
-static void matmul4(const float* A, const float* B, float* C)
-{
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < 4; j++) {
-            double s = 0.0;
-            for (int k = 0; k < 4; k++) s += (double)A[4 * i + k] * (double)B[4 * k + j];
-            C[4 * i + j] = (float)s;
-        }
 }
 
 // Frame::getPoseInverse (Core/Frame.cpp:137-153): Twc = [Rcw^T | Ow] with Ow = -Rcw^T tcw as one cv::gemm

@@ -138,10 +138,11 @@ def test_pnp_track_submit_collect_pipeline(pkg):
 
 @pytest.mark.parametrize("segments", [1, 2])
 def test_pnp_track_flag_chain_continuation_matches_oracle(pkg, oracle, segments):
-    """The flag chain through a pair whose RANSAC does not finish in the first hypothesis chunk (the pair
-    into a noise frame: no model reaches the inlier threshold, solvePnPRansac runs all its iterations on the
-    host continuation) and a failed solve's flags (every matched train index an outlier).  Bit for bit
-    against the oracle chain, before and after the failing pair."""
+    """The flag chain through a pair whose RANSAC does not finish in k_pnp_chain's first pass of hypotheses (the
+    pair into a noise frame: no model reaches the inlier threshold, so solvePnPRansac runs all its iterations,
+    pass after pass inside the kernel -- the flag chain has no host continuation) and a failed solve's flags
+    (every matched train index an outlier).  Bit for bit against the oracle chain, before and after the
+    failing pair."""
     import torch
     B = 9
     bgr, depth, gt, cam = synth_seq(B, seed=43, preset="fr1")
