@@ -279,17 +279,61 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
             const int lpc = np_max <= 16 ? 16 : np_max;
             if (lpc > 32) return fail(c, RGBD_ERR_UNSUPPORTED, "FAST cell interior wider than 64 px");
             const int cpw = 64 / lpc;
-            // a segment's staged row (16-B aligned start .. x1 + 6) must fit k_fast's kFastRowBytes = 160
+            // a plain segment's staged row (16-B aligned start .. x1 + 6) must fit kFastPlainRowBytes = 160
             auto row_bytes = [&](int q0, int e0) { return c->cells[e0 - 1].x1 + 6 - (c->cells[q0].x0 & ~15); };
+            auto plain_seg = [&](int q0, int e0) {
+                FastSeg s{{q0, q0, q0, q0}, (int16_t)(e0 - q0), (int16_t)lpc, 0, 0};
+                for (int k = 0; k < e0 - q0; k++) s.cell[k] = q0 + k;
+                return s;
+            };
+            // full waves stay plain segments; with RGBD_FAST_GATHER the short segments' cells (the n % cpw last
+            // cells of each cell row) are pooled by ROI height (the last cell row of a level may be shorter, and
+            // the walk's row bounds are wave-uniform) and packed cpw per wave into gathered segments
+            std::vector<FastSeg> full;
+            std::vector<std::pair<int, std::vector<int>>> pool;   // (ROI height, cells) in order of appearance
             for (int q = L.cell_begin; q < (int)c->cells.size();) {
                 int e = q + 1;
                 while (e < (int)c->cells.size() && e - q < cpw && c->cells[e].y0 == c->cells[q].y0 &&
-                       row_bytes(q, e + 1) <= 160)
+                       row_bytes(q, e + 1) <= kFastPlainRowBytes)
                     e++;
-                if (row_bytes(q, e) > 160) return fail(c, RGBD_ERR_UNSUPPORTED, "FAST segment row wider than 160 B");
-                c->segs.push_back(FastSeg{q, (int16_t)(e - q), (int16_t)lpc});
+                if (row_bytes(q, e) > kFastPlainRowBytes)
+                    return fail(c, RGBD_ERR_UNSUPPORTED, "FAST segment row wider than 160 B");
+                if (RGBD_FAST_GATHER && e - q < cpw) {
+                    const int ch = c->cells[q].y1 - c->cells[q].y0;
+                    auto it = pool.begin();
+                    while (it != pool.end() && it->first != ch) ++it;
+                    if (it == pool.end()) it = pool.insert(it, {ch, {}});
+                    for (int k = q; k < e; k++) it->second.push_back(k);
+                } else {
+                    full.push_back(plain_seg(q, e));
+                }
                 q = e;
             }
+            // the level's gathered segments lead its full ones, so they are never the last blocks of a frame
+            const int slot_bytes = kFastRowBytes / cpw / 4 * 4;
+            for (const auto& grp : pool) {
+                const std::vector<int>& v = grp.second;
+                for (size_t i = 0; i < v.size(); i += cpw) {
+                    const int n = (int)std::min(v.size() - i, (size_t)cpw);
+                    bool run = true;   // one run of a cell row: a plain segment after all
+                    for (int k = 1; k < n; k++)
+                        run = run && v[i + k] == v[i] + k && c->cells[v[i + k]].y0 == c->cells[v[i]].y0;
+                    if (run && row_bytes(v[i], v[i] + n) <= kFastPlainRowBytes) {
+                        c->segs.push_back(plain_seg(v[i], v[i] + n));
+                        continue;
+                    }
+                    FastSeg s{{v[i], v[i], v[i], v[i]}, (int16_t)n, (int16_t)lpc, 1, 0};
+                    for (int k = 0; k < n; k++) {
+                        const Cell& cc = c->cells[v[i + k]];
+                        // the slot holds the ROI row from its 4-B aligned start to the last lane's read (x1 + 6)
+                        if (align_up(cc.x1 + 6 - (cc.x0 & ~3), 4) > slot_bytes)
+                            return fail(c, RGBD_ERR_UNSUPPORTED, "FAST gathered segment slot wider than its share of 192 B");
+                        s.cell[k] = v[i + k];
+                    }
+                    c->segs.push_back(s);
+                }
+            }
+            c->segs.insert(c->segs.end(), full.begin(), full.end());
         }
         // DistributeOctTree roots (:420-422)
         const int dX = L.maxBX - L.minBX, dY = L.maxBY - L.minBY;

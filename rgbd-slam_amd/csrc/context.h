@@ -38,7 +38,7 @@ struct rgbd_ctx {
     rgbd_camera cam{};
     rgbd::ExtractCfg cfg{};              // host copy
     std::vector<rgbd::Cell> cells;
-    std::vector<rgbd::FastSeg> segs;     // k_fast segments (consecutive cells of one cell row)
+    std::vector<rgbd::FastSeg> segs;     // k_fast segments (per level: gathered leftovers, then full cell-row runs)
     std::string err;
 
     hipStream_t stream = nullptr;        // launch stream (own or external)

@@ -662,8 +662,13 @@ __device__ __forceinline__ void row_pairs(uint32_t d0, uint32_t d1, uint32_t d2,
     w[6] = __builtin_amdgcn_perm(hi, lo, 0x0c070c06u);
 }
 
-// One wave per segment: up to 64 / lpc consecutive cells of one cell row of one level (FastSeg).  The
-// segment's ROI rows are staged in LDS with 16-B loads (all in flight at once), then lane (cell k,
+// One wave per segment: up to 64 / lpc cells of one level with one ROI height (FastSeg): consecutive cells
+// of one cell row, or (gathered segments, RGBD_FAST_GATHER) the leftover cells of several cell rows, which
+// would each end their row in a mostly empty wave that walks every row at full cost.  A plain segment's
+// ROI rows are staged in LDS as one span with 16-B loads (all in flight at once); in a gathered segment
+// each slot's lanes stage their own cell with 4-B loads into the slot's column range of the 192-B row (a
+// 16-B aligned slot would need 64-80 B, and four do not fit the 10 KB of LDS that 16 workgroups per CU
+// leave each).  After the barrier both kinds run the same code: lane (cell k,
 // pair p) owns the pixel pair at ROI columns 3 + 2p, 4 + 2p of cell k and walks the cell's interior
 // rows top to bottom with the 7 rows x 7 pairs its ring needs in registers (the next row read one step
 // ahead).  Per row: m of both pixels (fast_m2), the row's horizontal maxima from the neighbour lanes
@@ -674,7 +679,6 @@ __device__ __forceinline__ void row_pairs(uint32_t d0, uint32_t d1, uint32_t d2,
 // survivor at iniThFAST walks again at minThFAST (:655-661).  Corners are emitted with pt relative to
 // the level's (minBorderX, minBorderY), i.e. vToDistributeKeys order.
 #define RGBD_FAST_WPE 4   // waves per SIMD: 126 VGPRs for the exit-free 7-row walk blocks (at 5 waves, 96 VGPRs, they spill 48; r05 same-box A/B against 5 waves with per-row exits: +0.6 %, k_fast 1.67 -> 1.65 ms)
-constexpr int kFastRowBytes = 160;   // staged segment row: <= 4 x 32 + 6 ROI bytes + 16-B alignment + over-read
 __device__ __forceinline__ void blur_thread(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur,
                                             const ExtractCfg& cfg, int b, int t);
 // k_fast's emission rank for 16-lane cells (one cell = one DPP row): corners below the lane over the whole
@@ -749,9 +753,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
     const int LPC = S.lpc;   // wave-uniform
     const int k = (lane >= LPC ? 1 : 0) + (lane >= 2 * LPC ? 1 : 0) + (lane >= 3 * LPC ? 1 : 0), p = lane - k * LPC;
     const bool cell_on = k < S.ncell;
-    const int ci = S.cell0 + (cell_on ? k : 0);
+    const int ci = k == 0 ? S.cell[0] : k == 1 ? S.cell[1] : k == 2 ? S.cell[2] : S.cell[3];   // unused slots: cell[0]
     const Cell c = cells[ci];
-    const Cell c0 = cells[S.cell0], cl = cells[S.cell0 + S.ncell - 1];
     const LevelCfg& L = cfg.lv[c.level];
     // ch is the same for every cell of the segment: wave-uniform, so the row loop's bound tests are scalar
     const int cw = c.x1 - c.x0, ch = __builtin_amdgcn_readfirstlane(c.y1 - c.y0);
@@ -761,7 +764,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
     const bool actB = act && 2 * p + 1 < a;          // pixel B evaluated (the second pixel of an odd end is not)
     // ---- stage ROI rows [0, ch), columns [xs, xs + 16 q) of the segment (xs 16-B aligned: rows are 64-B
     //      padded and level bases 256-B aligned)
-    {
+    int col0;   // byte column of the cell's ROI column 0 in the staged row
+    if (RGBD_FAST_GATHER && S.gathered) {
+        // gathered segment: the cells come from several cell rows, so slot k's lanes stage their own cell into
+        // the slot's column range of the row, lane (k, p) the dword p of every ROI row from the cell's 4-B
+        // aligned start up to x1 + 6 (the host checked that they fit the slot), 8 rows' loads in flight
+        const int sw = LPC <= 16 ? kFastRowBytes / 4 : LPC <= 21 ? kFastRowBytes / 3 : kFastRowBytes / 2;
+        const int xs = c.x0 & ~3;
+        const bool ld = cell_on && p < ((c.x1 + 6 - xs + 3) >> 2);
+        const uint8_t* src = pyr + (size_t)b * cfg.frame_pyr_bytes + L.off + (uint32_t)(c.y0 * L.stride + xs + 4 * p);
+        uint32_t* dst = roi + k * (sw >> 2) + p;
+        const int stride = L.stride;
+        for (int r0 = 0; r0 < ch; r0 += 8) {
+            uint32_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                v[u] = ld ? *reinterpret_cast<const uint32_t*>(src + (uint32_t)(min(r0 + u, ch - 1) * stride)) : 0u;
+#pragma unroll
+            for (int u = 0; u < 8; u++)
+                if (ld && r0 + u < ch) dst[(r0 + u) * (kFastRowBytes / 4)] = v[u];
+        }
+        col0 = (cell_on ? k : 0) * sw + (c.x0 & 3);   // lanes past the last cell read slot 0
+    } else {
+        const Cell c0 = cells[S.cell[0]], cl = cells[S.cell[0] + S.ncell - 1];
         const int xs = c0.x0 & ~15;
         const int q = (cl.x1 + 6 - xs + 15) >> 4;    // 16-B chunks per row (the walk reads up to x1 + 6)
         const uint8_t* src = pyr + (size_t)b * cfg.frame_pyr_bytes + L.off + (size_t)c0.y0 * L.stride + xs;
@@ -778,10 +803,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
             const uint4 v = *reinterpret_cast<const uint4*>(src + (uint32_t)(r * L.stride + 16 * j));
             *reinterpret_cast<uint4*>(&roi[r * (kFastRowBytes / 4) + 4 * j]) = v;
         }
+        col0 = c.x0 - xs;
     }
     __syncthreads();
     FAST_PROF(1);
-    const int off = c.x0 + (act ? 2 * p : 0) - (c0.x0 & ~15);   // byte column of this lane's 8 bytes
+    const int off = col0 + (act ? 2 * p : 0);   // byte column of this lane's 8 bytes
     const uint32_t sh = (uint32_t)off & 3u;
     const uint32_t* rp = roi + (off >> 2);
     auto rd3 = [&](int y, uint32_t& d0, uint32_t& d1, uint32_t& d2) {

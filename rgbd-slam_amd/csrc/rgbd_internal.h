@@ -113,11 +113,26 @@ struct Cell {                  // one FAST ROI (rowRange/colRange of :655-660), 
     int16_t level, x0, y0, x1, y1, pad;
 };
 
-struct FastSeg {               // k_fast: up to 64 / lpc consecutive cells of one cell row of one level
-    int32_t cell0;             // first cell (index into the cell table)
+// k_fast, 0 / 1 for A/B builds: the leftover cells of a level's cell rows packed into full waves (host table +
+// staging; 640 x 480: 229 -> 215 segments per frame, step 4.12 -> 4.06 ms, profiles/fast_pack_emit)
+#ifndef RGBD_FAST_GATHER
+#define RGBD_FAST_GATHER 1
+#endif
+
+// k_fast's staged segment row.  A plain segment's cells lie side by side from a 16-B aligned start (<= 160 B);
+// a gathered segment gives each of its 64 / lpc slots kFastRowBytes / (64 / lpc) bytes (48 / 64 / 96), which
+// hold the cell's ROI row from its 4-B aligned start up to the last lane's 12-byte read (x1 + 6)
+constexpr int kFastRowBytes = 192;
+constexpr int kFastPlainRowBytes = 160;
+
+struct FastSeg {               // k_fast: up to 64 / lpc cells of one level with one ROI height
+    int32_t cell[4];           // slot k's cell (index into the cell table), k < ncell
     int16_t ncell;             // cells in the segment
     int16_t lpc;               // lanes per cell: 16 (interior <= 32 px wide, one DPP row) or the level's widest
                                // cell's pixel pairs, 17 .. 32 (so 3 cells of 17-21 pairs share a wave)
+    int16_t gathered;          // 0: consecutive cells of one cell row, staged as one span; 1: the leftover cells
+                               // of several cell rows (RGBD_FAST_GATHER), each staged into its own slot
+    int16_t pad;
 };
 
 struct ResizeX { int16_t sx, a0, a1, pad; };   // xofs + ialpha
