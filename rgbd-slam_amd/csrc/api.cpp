@@ -351,7 +351,7 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
     for (int l = 0; l < nl; l++) {
         LevelCfg& L = C.lv[l];
         L.key_off = key_off;
-        L.key_cap = L.cell_count * cell_cap;
+        L.key_cap = align_up(L.cell_count * cell_cap, 4);   // k_distribute reads keys and state four at a time
         key_off += L.key_cap;
         if (L.key_cap >= (1 << 24)) return fail(c, RGBD_ERR_UNSUPPORTED, "too many FAST candidates per level");
     }
@@ -367,15 +367,14 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
         for (int l = 0; l < nl; l++) mc = std::max(mc, C.lv[l].cell_count);
         C.scan_cap = std::max(NC, mc) + 1;
     }
-    // quadtree round state in LDS: per candidate its u32 key + its node id (u8 while node_cap <= 256, else
-    // u16), within RGBD_DIST_LDS_KB per workgroup (four 512-thread workgroups per CU); a level with more
-    // candidates keeps it in HBM.  Round 4 (level-major dispatch): 32 / 38 / 44 / 52 / 80 KB measured
-    // 0.54 / 0.53 / 0.62 / 0.61 / 0.74 ms per 1024 frames -- occupancy beats residency for this latency-bound kernel
-    {
-        const int per_key = 4 + (NC <= 256 ? 1 : 2);
-        const long room = (long)RGBD_DIST_LDS_KB * 1024 - (long)distribute_lds_bytes(NC, C.scan_cap);
-        C.dist_kc = room > 0 ? (int)(room / per_key / 64 * 64) : 0;
-    }
+    // quadtree round state in LDS: per candidate its u32 key + its state, node index and quadrant in that node
+    // (a u8 + 2 bits while node_cap <= 256, else a u16), within RGBD_DIST_LDS_KB per workgroup (four 512-thread
+    // workgroups per CU).  At node_cap 256 (1000 features, 640 x 480: 280 level-0 cells) the node arrays take
+    // 24,272 B and leave 2,768 keys with their state (14,532 B); a level with more candidates keeps its keys in
+    // HBM and its state alone in that region (1.25 B each: up to 11.6k candidates), and past that both in HBM.  Round 4
+    // (level-major dispatch): 32 / 38 / 44 / 52 / 80 KB measured 0.54 / 0.53 / 0.62 / 0.61 / 0.74 ms per 1024
+    // frames -- occupancy beats residency for this latency-bound kernel
+    C.dist_kc = distribute_key_capacity((long)RGBD_DIST_LDS_KB * 1024 - (long)distribute_lds_bytes(NC, C.scan_cap), NC);
     C.kp_cap = align_up(sel_off, 4);
     // resize tables (level l from level l-1)
     for (int l = 1; l < nl; l++)

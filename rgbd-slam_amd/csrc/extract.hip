@@ -1132,10 +1132,82 @@ __device__ int block_scan_excl(int* a, int n, int* wsum)
 }
 
 #define RGBD_DIST_WPE 8
-// NodeT: the per-key node id in LDS (uint8_t while node_cap <= 256, i.e. nfeatures <= ~1700; else uint16_t).
+// Where a level's per-round key state lives, chosen once per workgroup; each case runs its own instantiation of
+// the gather and key-pass bodies (as FastLg4 / FastLgN in k_fast), so no key loop tests the location per access.
+struct DistLL { static constexpr bool keysL = true, stateL = true; };     // keys and state in LDS
+struct DistGL { static constexpr bool keysL = false, stateL = true; };    // state in LDS, keys in the HBM scratch
+struct DistGG { static constexpr bool keysL = false, stateL = false; };   // both in the HBM scratch
+struct DistMid { static constexpr bool last = false; };
+struct DistLast { static constexpr bool last = true; };
+
+// Per-key round state: 4 * (the key's node, as an index into the current list) + (the key's quadrant in that
+// node's box, meaningful only while the node holds more than one key): the index of the key's entry in the
+// round's destination table.  A thread owns the same groups of four consecutive keys in every pass.
+template <bool Planes>
+struct DistState;
+// u8 node ids, four keys' to a dword, and a plane of 2-bit quadrants, four keys' to a byte (LDS, node_cap <= 256):
+// 1.25 bytes per key
+template <>
+struct DistState<true> {
+    uint32_t* nd;
+    uint8_t* qd;
+    __device__ __forceinline__ void load4(int g, int (&s)[4]) const
+    {
+        const uint32_t w = nd[g], q = qd[g];
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j] = (int)((((w >> (8 * j)) & 255u) << 2) | ((q >> (2 * j)) & 3u));
+    }
+    __device__ __forceinline__ void store4(int g, const int (&ni)[4], const int (&q)[4]) const
+    {
+        nd[g] = (uint32_t)ni[0] | ((uint32_t)ni[1] << 8) | ((uint32_t)ni[2] << 16) | ((uint32_t)ni[3] << 24);
+        qd[g] = (uint8_t)(q[0] | (q[1] << 2) | (q[2] << 4) | (q[3] << 6));
+    }
+    // gather: a key's root (several roots), or its quadrant in the one root (both planes zeroed before)
+    __device__ __forceinline__ void init_node(int k, int node) const { reinterpret_cast<uint8_t*>(nd)[k] = (uint8_t)node; }
+    __device__ __forceinline__ void init_quad(int k, int q) const
+    {
+        if (q) atomicOr(reinterpret_cast<uint32_t*>(qd) + (k >> 4), (uint32_t)q << (2 * (k & 15)));
+    }
+    __device__ __forceinline__ int node_of(int k) const { return reinterpret_cast<const uint8_t*>(nd)[k]; }
+};
+// u16 4 * node + quadrant (node_cap <= 4096), in LDS or in the HBM scratch
+template <>
+struct DistState<false> {
+    uint16_t* st;
+    __device__ __forceinline__ void load4(int g, int (&s)[4]) const
+    {
+        const uint2 w = *reinterpret_cast<const uint2*>(st + 4 * g);
+        s[0] = (int)(w.x & 0xFFFFu);
+        s[1] = (int)(w.x >> 16);
+        s[2] = (int)(w.y & 0xFFFFu);
+        s[3] = (int)(w.y >> 16);
+    }
+    __device__ __forceinline__ void store4(int g, const int (&ni)[4], const int (&q)[4]) const
+    {
+        uint2 w;
+        w.x = (uint32_t)(4 * ni[0] + q[0]) | ((uint32_t)(4 * ni[1] + q[1]) << 16);
+        w.y = (uint32_t)(4 * ni[2] + q[2]) | ((uint32_t)(4 * ni[3] + q[3]) << 16);
+        *reinterpret_cast<uint2*>(st + 4 * g) = w;
+    }
+    __device__ __forceinline__ void init_node(int k, int node) const { st[k] = (uint16_t)(4 * node); }
+    __device__ __forceinline__ void init_quad(int k, int q) const { st[k] = (uint16_t)q; }
+    __device__ __forceinline__ int node_of(int k) const { return st[k] >> 2; }
+};
+
+// LDS of k_distribute's node arrays, before the key region (16-byte aligned for the keys' 128-bit reads):
+// sortkey 8NC + childcnt x2 32NC + tmp/tmp2 8SC + size/cid A,B 16NC + best 4NC + dest 8NC + ord 2NC + bbox A,B 16NC
+__host__ __device__ constexpr size_t dist_node_bytes(int NC, int SC)
+{
+    return (((size_t)NC * 86 + (size_t)SC * 8) + 15) & ~(size_t)15;
+}
+// ... and of the key region for kc keys (kc a multiple of 16): the u32 keys + their state
+__host__ __device__ constexpr size_t dist_key_bytes(int kc, bool u8) { return (size_t)kc * 4 + (size_t)(kc >> 2) * (u8 ? 5 : 8); }
+
+// NodeT: the per-key state's form in LDS (uint8_t: node-id and quadrant planes, while node_cap <= 256, i.e.
+// nfeatures <= ~1700; else uint16_t).
 // Levels [l0, l0 + nlv) of every frame, one workgroup each; kc = the keys per level whose round state (the
-// u32 key as FAST wrote it + the node id) fits in this launch's LDS.  A level with more candidates keeps it
-// in the HBM scratch (keys_g / node_g) instead -- correct for any count, but every round then goes to memory.
+// u32 key as FAST wrote it + the node / quadrant state) fits in this launch's LDS.  A level with more candidates
+// keeps it in the HBM scratch (keys_g / node_g) instead -- correct for any count, but every round then goes to memory.
 template <typename NodeT>
 __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RGBD_DIST_WPE, 8))) void k_distribute(const int* __restrict__ cell_count,
                                                              const uint32_t* __restrict__ cell_slots,
@@ -1176,13 +1248,14 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     int* sizeB = cidA + NC;
     int* cidB = sizeB + NC;
     int* best = cidB + NC;                                                               // NC
-    int16_t* childIdx = reinterpret_cast<int16_t*>(best + NC);                           // 4 NC
-    int16_t* newIdx = childIdx + 4 * NC;                                                 // NC
-    int16_t* ord = newIdx + NC;                                                          // NC
+    // a round's destination table: entry 4 * node + quadrant = the new list index of a key in that quadrant of
+    // that node (a divided node: its child; a surviving node: its own new index in all four entries), bit 15
+    // set on a fresh child with more than one key (the keys that are counted for the next round)
+    uint16_t* dest = reinterpret_cast<uint16_t*>(best + NC);                             // 4 NC
+    int16_t* ord = reinterpret_cast<int16_t*>(dest + 4 * NC);                            // NC
     int16_t* bxA = ord + NC;                                                             // 4 NC (x0,y0,x1,y1)
     int16_t* bxB = bxA + 4 * NC;                                                         // 4 NC
-    uint32_t* kk32 = reinterpret_cast<uint32_t*>(bxB + 4 * NC);                          // kc keys: x | y << 11 | score << 22
-    NodeT* kno = reinterpret_cast<NodeT*>(kk32 + kc);                                    // kc node ids
+    uint32_t* kk32 = reinterpret_cast<uint32_t*>(smem + dist_node_bytes(NC, SC));        // kc keys: x | y << 11 | score << 22
     __shared__ int wsum[kDistThreads / 64];
     __shared__ int s_J;
 
@@ -1206,35 +1279,80 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     for (int i = tid; i < nCells; i += kDistThreads) tmp2[i] = tmp[i];
     __syncthreads();
     const int n = block_scan_excl(tmp2, nCells, wsum);   // tmp2 = offsets, tmp = counts
-    // the per-round key state (the key as FAST wrote it + its node id) lives in LDS when it fits, else in HBM
-    // Per-round key state: the key as FAST wrote it + its node id.  Both in LDS when they fit (inL); else the node
-    // ids alone in the same LDS region (ndL: the level's keys are written to the HBM scratch once by the gather
+    // Per-round key state: the key as FAST wrote it + its DistState.  Both in LDS when they fit (inL); else the
+    // state alone in the same LDS region (ndL: the level's keys are written to the HBM scratch once by the gather
     // and only read after it, so no division round writes to HBM); else both in the HBM scratch
+    constexpr bool kU8 = sizeof(NodeT) == 1;
+    const int n4 = (n + 3) >> 2;   // groups of four keys
     const bool inL = n <= kc;
-    const bool ndL = !inL && n * (int)sizeof(NodeT) <= kc * (4 + (int)sizeof(NodeT));
-    NodeT* kndL = reinterpret_cast<NodeT*>(kk32);   // ndL: node ids from the region's start
-    auto key_at = [&](int kk) -> uint32_t { return inL ? kk32[kk] : keys[kk]; };
-    auto nd_get = [&](int kk) -> int { return inL ? (int)kno[kk] : (ndL ? (int)kndL[kk] : (int)nodeOf[kk]); };
-    auto nd_set = [&](int kk, int v) {
+    const bool ndL = !inL && (kU8 ? 4 * n4 + ((n4 + 3) & ~3) : 8 * n4) <= (int)dist_key_bytes(kc, kU8);
+    auto with_loc = [&](auto&& f) __attribute__((always_inline)) {
         if (inL)
-            kno[kk] = (NodeT)v;
+            f(DistLL{});
         else if (ndL)
-            kndL[kk] = (NodeT)v;
+            f(DistGL{});
         else
-            nodeOf[kk] = (uint16_t)v;
+            f(DistGG{});
     };
-    {
+    auto state_of = [&](auto loc) __attribute__((always_inline)) {
+        using Loc = decltype(loc);
+        DistState<kU8 && Loc::stateL> st;
+        if constexpr (kU8 && Loc::stateL) {
+            st.nd = Loc::keysL ? kk32 + kc : kk32;   // behind the keys, or (ndL) from the region's start
+            st.qd = reinterpret_cast<uint8_t*>(st.nd + n4);
+        } else if constexpr (Loc::stateL) {
+            st.st = reinterpret_cast<uint16_t*>(Loc::keysL ? kk32 + kc : kk32);
+        } else {
+            st.st = nodeOf;
+        }
+        return st;
+    };
+    // four consecutive keys of group g (the key region and every level's scratch hold a multiple of four)
+    auto keys4 = [&](auto loc, int g) __attribute__((always_inline)) -> uint4 {
+        if constexpr (decltype(loc)::keysL)
+            return *reinterpret_cast<const uint4*>(kk32 + 4 * g);
+        else
+            return *reinterpret_cast<const uint4*>(keys + 4 * g);
+    };
+    // One root (nIni == 1: any image wider than tall and < 1.5x as wide, every 640 x 480 level): its box is
+    // known before any key is read, so the root list, its size and the zeroed child counts are set here and the
+    // gather itself counts every key's root quadrant and writes its first state (no root pass)
+    const int rootX1 = (int)hX, rootY1 = LV.maxBY - LV.minBY;
+    const int rootMx = (rootX1 + 1) >> 1, rootMy = (rootY1 + 1) >> 1;   // quad_of's midpoints of (0, 0, rootX1, rootY1)
+    if (nIni == 1) {
+        if (tid == 0) {
+            sizeB[0] = n;
+            cidB[0] = 0;
+            bxB[0] = 0;
+            bxB[1] = 0;
+            bxB[2] = (int16_t)rootX1;
+            bxB[3] = (int16_t)rootY1;
+            s_J = n > 0 ? 1 : 0;
+        }
+        if (tid < 4) childcnt[tid] = 0;
+        if constexpr (kU8) {
+            if (inL || ndL) {   // node ids 0, quadrants or-ed in by the gather
+                uint32_t* z = inL ? kk32 + kc : kk32;
+                for (int i = tid; i < n4 + ((n4 + 3) >> 2); i += kDistThreads) z[i] = 0u;
+            }
+        }
+        __syncthreads();
+    }
+    with_loc([&](auto loc) __attribute__((always_inline)) {
+        using Loc = decltype(loc);
+        const auto st = state_of(loc);
         const int w = tid >> 6, sub = (tid >> 4) & 3, l16 = tid & 15;
         constexpr int kCStep = 4 * (kDistThreads / 64);   // cells per workgroup step
-        // two cell groups per step, the first 16 keys of each loaded before either is processed
-        for (int c00 = 4 * w; c00 < nCells; c00 += 2 * kCStep) {
-            int cntg[2], og[2], tripsg[2];
-            const uint32_t* srcg[2];
-            uint32_t v0g[2];
-            // every key of the first kPre trips of both groups loaded before any is processed (one global
-            // round trip per step instead of one per trip: level-0 cells hold ~34 keys, three trips)
-            constexpr int kPre = 4;
+        // two cell groups per step; every key of the first kPre trips of both groups loaded before any is
+        // processed (one global round trip per step instead of one per trip: level-0 cells hold ~34 keys, three
+        // trips).  Loading the next step's groups ahead of this step's keys measured no gain.
+        constexpr int kPre = 4;
+        struct Step {
+            int cnt[2], o[2], trips[2];
+            const uint32_t* src[2];
             uint32_t vpre[2][kPre];
+        };
+        auto issue = [&](int c00, Step& S) __attribute__((always_inline)) {
 #pragma unroll
             for (int g = 0; g < 2; g++) {
                 const int ci = c00 + g * kCStep + sub;
@@ -1242,18 +1360,22 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                 int trips = (ci < nCells) ? (tmp[ci] + 15) >> 4 : 0;
 #pragma unroll
                 for (int o = 16; o < 64; o <<= 1) trips = max(trips, __shfl_xor(trips, o, 64));
-                tripsg[g] = trips;
-                cntg[g] = (ci < nCells) ? tmp[ci] : 0;
-                og[g] = (ci < nCells) ? tmp2[ci] : 0;
-                srcg[g] = cell_slots + ((size_t)b * cfg.n_cells + LV.cell_begin + (ci < nCells ? ci : 0)) * cfg.cell_cap;
+                S.trips[g] = trips;
+                S.cnt[g] = (ci < nCells) ? tmp[ci] : 0;
+                S.o[g] = (ci < nCells) ? tmp2[ci] : 0;
+                S.src[g] = cell_slots + ((size_t)b * cfg.n_cells + LV.cell_begin + (ci < nCells ? ci : 0)) * cfg.cell_cap;
 #pragma unroll
-                for (int t = 0; t < kPre; t++) vpre[g][t] = l16 + 16 * t < cntg[g] ? srcg[g][l16 + 16 * t] : 0u;
+                for (int t = 0; t < kPre; t++) S.vpre[g][t] = l16 + 16 * t < S.cnt[g] ? S.src[g][l16 + 16 * t] : 0u;
             }
-            (void)v0g;
+        };
+        for (int c00 = 4 * w; c00 < nCells; c00 += 2 * kCStep) {
+            Step S;
+            issue(c00, S);
+            auto& vpre = S.vpre;
 #pragma unroll
             for (int g = 0; g < 2; g++) {
-            const int trips = tripsg[g], cnt = cntg[g], o = og[g];
-            const uint32_t* src = srcg[g];
+            const int trips = S.trips[g], cnt = S.cnt[g], o = S.o[g];
+            const uint32_t* src = S.src[g];
             for (int tr = 0; tr < trips; tr++) {
                 const int j = l16 + 16 * tr;
                 const bool on = j < cnt;
@@ -1267,27 +1389,26 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                     } else {
                         v = src[j];
                     }
-                    // one root (nIni == 1: any image wider than tall and < 1.5x as wide, every 640 x 480
-                    // level): no division, no root count (the root holds all n keys, set below) and no node
-                    // id (the root pass writes every key's)
+                    if constexpr (Loc::keysL)
+                        kk32[o + j] = v;
+                    else
+                        keys[o + j] = v;
+                    // several roots: the key's root, counted into the root sizes; one root: the key's
+                    // quadrant in the root box, counted into the first round's child counts
                     if (nIni > 1) {
                         idx = (int)((float)(int)(v & 2047u) / hX);
                         idx = min(max(idx, 0), nIni - 1);
-                    }
-                    if (inL) {
-                        kk32[o + j] = v;
-                        if (nIni > 1) kno[o + j] = (NodeT)idx;
+                        st.init_node(o + j, idx);
                     } else {
-                        keys[o + j] = v;
-                        if (nIni > 1) nd_set(o + j, idx);
+                        idx = ((int)(v & 2047u) < rootMx ? 0 : 1) | ((int)((v >> 11) & 2047u) < rootMy ? 0 : 2);
+                        st.init_quad(o + j, idx);
                     }
                 }
-                if (nIni > 1) lds_count(sizeA, idx, on);
+                lds_count(nIni > 1 ? sizeA : childcnt, idx, on && (nIni > 1 || n > 1));
             }
             }
         }
-    }
-    if (nIni == 1 && tid == 0) sizeA[0] = n;
+    });
     __threadfence_block();
     __syncthreads();
     DIST_PROF(1);
@@ -1298,7 +1419,7 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     int* sz = sizeB; int* cd = cidB; int16_t* bx = bxB;
     int* szN = sizeA; int* cdN = cidA; int16_t* bxN = bxA;
     int* cc = childcnt; int* ccN = childcnt2;
-    if (tid < 64) {
+    if (nIni > 1 && tid < 64) {
         int carry = 0;
         for (int base = 0; base < nIni; base += 64) {
             const int i = base + lane;
@@ -1319,36 +1440,35 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
         for (int i = lane; i < 4 * carry; i += 64) cc[i] = 0;
         if (lane == 0) s_J = carry;
     }
-    __syncthreads();
+    if (nIni > 1) __syncthreads();   // (one root: s_J was set before the gather)
     int L = s_J;
-    // root ids -> compacted ids, fused with the first round's child counts: two keys per thread per step, the
-    // next step's keys loaded ahead (as in the division rounds below)
-    {
-        constexpr int kStep = 2 * kDistThreads;
-        uint32_t kpa = n > 0 ? key_at(tid < n ? tid : n - 1) : 0u;
-        uint32_t kpb = n > 0 ? key_at(tid + kDistThreads < n ? tid + kDistThreads : n - 1) : 0u;
-        for (int k0 = 0; k0 < n; k0 += kStep) {
-            const int ka = k0 + tid, kb = ka + kDistThreads;
-            const int ca = ka < n ? ka : n - 1, cb = kb < n ? kb : n - 1;   // clamped loads; stores / counts masked
-            const uint32_t va = kpa, vb = kpb;
-            if (k0 + kStep < n) {
-                kpa = key_at(ka + kStep < n ? ka + kStep : n - 1);
-                kpb = key_at(kb + kStep < n ? kb + kStep : n - 1);
+    // several roots: root ids -> compacted ids, fused with the first round's child counts (four keys per thread
+    // per step, the next step's keys loaded ahead, as in the division rounds below)
+    if (nIni > 1) {
+        with_loc([&](auto loc) __attribute__((always_inline)) {
+            const auto st = state_of(loc);
+            uint4 kp = n4 > 0 ? keys4(loc, min(tid, n4 - 1)) : make_uint4(0u, 0u, 0u, 0u);
+            for (int g0 = 0; g0 < n4; g0 += kDistThreads) {
+                const int g = g0 + tid, gc = min(g, n4 - 1);   // clamped loads; stores / counts masked
+                const uint4 kv = kp;
+                if (g0 + kDistThreads < n4) kp = keys4(loc, min(g + kDistThreads, n4 - 1));
+                const uint32_t v[4] = {kv.x, kv.y, kv.z, kv.w};
+                int s[4], ni[4], q[4];
+                st.load4(gc, s);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const bool on = 4 * g + j < n;
+                    const int r = tmp[on ? s[j] >> 2 : 0];
+                    ni[j] = on ? r : 0;
+                    q[j] = quad_in((int)(v[j] & 2047u), (int)((v[j] >> 11) & 2047u), bx, ni[j]);
+                    lds_count(cc, 4 * ni[j] + q[j], on && sz[ni[j]] > 1);
+                }
+                if (g < n4) st.store4(g, ni, q);
             }
-            const int nda = nIni == 1 ? 0 : tmp[nd_get(ca)], ndb = nIni == 1 ? 0 : tmp[nd_get(cb)];
-            const int xa = (int)(va & 2047u), ya = (int)((va >> 11) & 2047u);
-            const int xb = (int)(vb & 2047u), yb = (int)((vb >> 11) & 2047u);
-            const bool ona = ka < n && sz[nda] > 1, onb = kb < n && sz[ndb] > 1;
-            const int ta = ona ? 4 * nda + quad_in(xa, ya, bx, nda) : 0;
-            const int tb = onb ? 4 * ndb + quad_in(xb, yb, bx, ndb) : 0;
-            if (ka < n) nd_set(ka, nda);
-            if (kb < n) nd_set(kb, ndb);
-            lds_count(cc, ta, ona);
-            lds_count(cc, tb, onb);
-        }
+        });
+        __threadfence_block();
+        __syncthreads();
     }
-    __threadfence_block();
-    __syncthreads();
 
     DIST_PROF(2);
     // ---- division rounds.  Node bookkeeping (order, child offsets, survivors) runs on wave 0 with
@@ -1447,19 +1567,21 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
             const int nApply = (phase == 2 && J < nS) ? J + 1 : nS;
             wave_lds_sync();
             const int T = (nApply > 0) ? tmp[nApply - 1] + tmp2[nApply - 1] : 0;
-            for (int i = lane; i < L; i += 64) newIdx[i] = 0;
+            // (a node's first destination entry marks it divided until the entries are written)
+            for (int i = lane; i < L; i += 64) dest[4 * i] = 0;
             wave_lds_sync();
-            for (int j = lane; j < nApply; j += 64) newIdx[ord[j]] = -1;
+            for (int j = lane; j < nApply; j += 64) dest[4 * ord[j]] = 0xFFFFu;
             wave_lds_sync();
             // survivors keep their order behind the new children
             int sv = 0;
             for (int base = 0; base < L; base += 64) {
                 const int i = base + lane;
-                const bool f = i < L && newIdx[i] == 0;
+                const bool f = i < L && dest[4 * i] == 0;
                 const unsigned long long bal = __ballot(f);
                 if (f) {
                     const int ni = T + sv + __popcll(bal & lanes_below);
-                    newIdx[i] = (int16_t)ni;
+                    const uint32_t d2 = (uint32_t)ni | ((uint32_t)ni << 16);
+                    *reinterpret_cast<uint2*>(dest + 4 * i) = make_uint2(d2, d2);
                     szN[ni] = sz[i];
                     cdN[ni] = cd[i];
 #pragma unroll
@@ -1485,7 +1607,7 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                         bxN[4 * ni + 1] = (int16_t)cy0;
                         bxN[4 * ni + 2] = (int16_t)cx1;
                         bxN[4 * ni + 3] = (int16_t)cy1;
-                        childIdx[4 * nd + q] = (int16_t)ni;
+                        dest[4 * nd + q] = (uint16_t)(ni | (cnt > 1 ? 0x8000 : 0));
                         o++;
                     }
                 }
@@ -1506,41 +1628,42 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
         DIST_PROF(20 + rounds);
         const int T = s_round[0], Lnew = s_round[1], nToExpand = s_round[2];
         const bool last = s_round[3] != 0;
-        // two keys per thread per step (their dependent LDS chains -- node id -> new index -> child slot ->
-        // size -> box -- interleaved), the next step's two keys loaded before them, so the keys' L2 round
-        // trips (levels whose keys live in the HBM scratch) and the chains overlap
-        constexpr int kStep = 2 * kDistThreads;
-        uint32_t kpa = n > 0 ? key_at(tid < n ? tid : n - 1) : 0u;
-        uint32_t kpb = n > 0 ? key_at(tid + kDistThreads < n ? tid + kDistThreads : n - 1) : 0u;
-        for (int k0 = 0; k0 < n; k0 += kStep) {
-            const int ka = k0 + tid, kb = ka + kDistThreads;
-            const int ca = ka < n ? ka : n - 1, cb = kb < n ? kb : n - 1;   // clamped loads; stores / counts masked
-            const uint32_t va = kpa, vb = kpb;
-            if (k0 + kStep < n) {
-                kpa = key_at(ka + kStep < n ? ka + kStep : n - 1);
-                kpb = key_at(kb + kStep < n ? kb + kStep : n - 1);
+        // four consecutive keys per thread per step (one state read and write, one 128-bit key read; their
+        // dependent LDS chains -- state -> destination -> child box -- interleaved), the next step's keys
+        // loaded before them, so the keys' L2 round trips (levels whose keys live in the HBM scratch) and
+        // the chains overlap.  Every round but the last has divided every node with more than one key, so only
+        // a key whose destination is a fresh child with more than one key (bit 15) is counted for the next round.
+        auto key_pass = [&](auto loc, auto rnd) __attribute__((always_inline)) {
+            const auto st = state_of(loc);
+            uint4 kp = n4 > 0 ? keys4(loc, min(tid, n4 - 1)) : make_uint4(0u, 0u, 0u, 0u);
+            for (int g0 = 0; g0 < n4; g0 += kDistThreads) {
+                const int g = g0 + tid, gc = min(g, n4 - 1);   // clamped loads; stores / counts masked
+                const uint4 kv = kp;
+                if (g0 + kDistThreads < n4) kp = keys4(loc, min(g + kDistThreads, n4 - 1));
+                const uint32_t v[4] = {kv.x, kv.y, kv.z, kv.w};
+                int s[4], ni[4], q[4];
+                st.load4(gc, s);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int k = 4 * g + j;
+                    const bool on = k < n;
+                    const unsigned int d = dest[on ? s[j] : 0];
+                    ni[j] = (int)(d & 0x7FFFu);
+                    if constexpr (decltype(rnd)::last) {
+                        lds_max(ubest, ni[j], ((unsigned int)key_s(v[j]) << 24) | (unsigned int)(0xFFFFFF - k), on);
+                    } else {
+                        q[j] = quad_in((int)(v[j] & 2047u), (int)((v[j] >> 11) & 2047u), bxN, ni[j]);
+                        lds_count(ccN, 4 * ni[j] + q[j], on && (d & 0x8000u) != 0u);
+                    }
+                }
+                if constexpr (!decltype(rnd)::last)
+                    if (g < n4) st.store4(g, ni, q);
             }
-            const int nda = nd_get(ca), ndb = nd_get(cb);
-            const int xa = (int)(va & 2047u), ya = (int)((va >> 11) & 2047u);
-            const int xb = (int)(vb & 2047u), yb = (int)((vb >> 11) & 2047u);
-            int nia = newIdx[nda], nib = newIdx[ndb];
-            const int cia = childIdx[4 * nda + quad_in(xa, ya, bx, nda)], cib = childIdx[4 * ndb + quad_in(xb, yb, bx, ndb)];
-            nia = nia < 0 ? cia : nia;
-            nib = nib < 0 ? cib : nib;
-            if (last) {
-                lds_max(ubest, nia, ((unsigned int)key_s(va) << 24) | (unsigned int)(0xFFFFFF - ka), ka < n);
-                lds_max(ubest, nib, ((unsigned int)key_s(vb) << 24) | (unsigned int)(0xFFFFFF - kb), kb < n);
-            } else {
-                const int sna = szN[nia], snb = szN[nib];
-                const bool ona = ka < n && sna > 1, onb = kb < n && snb > 1;
-                const int ta = ona ? 4 * nia + quad_in(xa, ya, bxN, nia) : 0;
-                const int tb = onb ? 4 * nib + quad_in(xb, yb, bxN, nib) : 0;
-                if (ka < n) nd_set(ka, nia);
-                if (kb < n) nd_set(kb, nib);
-                lds_count(ccN, ta, ona);
-                lds_count(ccN, tb, onb);
-            }
-        }
+        };
+        if (last)
+            with_loc([&](auto loc) __attribute__((always_inline)) { key_pass(loc, DistLast{}); });
+        else
+            with_loc([&](auto loc) __attribute__((always_inline)) { key_pass(loc, DistMid{}); });
         __threadfence_block();
         __syncthreads();
         // swap buffers
@@ -1567,15 +1690,22 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     if (!best_done) {   // no division round ran
         for (int i = tid; i < L; i += kDistThreads) ubest[i] = 0u;
         __syncthreads();
-        for (int k = tid; k < n; k += kDistThreads)
-            atomicMax(&ubest[nd_get(k)], ((unsigned int)key_s(key_at(k)) << 24) | (unsigned int)(0xFFFFFF - k));
+        with_loc([&](auto loc) __attribute__((always_inline)) {
+            const auto st = state_of(loc);
+            const uint32_t* kbuf = decltype(loc)::keysL ? kk32 : keys;
+            for (int k = tid; k < n; k += kDistThreads)
+                atomicMax(&ubest[st.node_of(k)], ((unsigned int)key_s(kbuf[k]) << 24) | (unsigned int)(0xFFFFFF - k));
+        });
     }
     __syncthreads();
     uint32_t* out = sel + (size_t)b * cfg.sel_per_frame + LV.sel_off;
-    for (int i = tid; i < L; i += kDistThreads) {
-        const int k = 0xFFFFFF - (int)(ubest[i] & 0xFFFFFFu);
-        out[i] = key_at(k);
-    }
+    with_loc([&](auto loc) __attribute__((always_inline)) {
+        const uint32_t* kbuf = decltype(loc)::keysL ? kk32 : keys;
+        for (int i = tid; i < L; i += kDistThreads) {
+            const int k = 0xFFFFFF - (int)(ubest[i] & 0xFFFFFFu);
+            out[i] = kbuf[min(k, n - 1)];   // (every node holds a key; the clamp keeps a broken list inside the level)
+        }
+    });
     if (tid == 0) sel_count[b * cfg.nlevels + level] = L;
 #ifdef RGBD_PNP_PROFILE
     if (threadIdx.x == 0 && b == 0 && level < 4) { g_dist_prof[level][42] = clock64(); g_dist_prof[level][43] = rounds; g_dist_prof[level][44] = n; g_dist_prof[level][45] = phase; g_dist_prof[level][47] = wall_clock64(); }
@@ -2147,10 +2277,15 @@ hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* seg
 
 size_t distribute_lds_bytes(int NC, int SC)
 {
-    // sortkey 8NC + childcnt x2 32NC + tmp/tmp2 8SC + size/cid A,B 16NC + best 4NC
-    // + childIdx 8NC + newIdx 2NC + ord 2NC + bbox A,B 16NC
-    return (size_t)NC * 8 + (size_t)NC * 32 + (size_t)SC * 8 + (size_t)NC * 16 + (size_t)NC * 4
-           + (size_t)NC * 8 + (size_t)NC * 2 + (size_t)NC * 2 + (size_t)NC * 16 + 64;
+    return dist_node_bytes(NC, SC) + 64;   // the node arrays + the kernel's static LDS
+}
+
+int distribute_key_capacity(long room, int NC)
+{
+    // per group of four keys: 16 bytes of keys + their state (u8 node ids + 2-bit quadrants: 5 bytes; u16: 8);
+    // a multiple of 16 keys keeps the quadrant plane whole dwords
+    const int per4 = 16 + (NC <= 256 ? 5 : 8);
+    return room > 0 ? (int)(room / per4 * 4 / 16 * 16) : 0;
 }
 
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,
@@ -2158,7 +2293,7 @@ hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, 
                        uint32_t* sel, int* err, int B, hipStream_t st)
 {
     const bool u8 = node_cap <= 256;
-    const size_t lds = distribute_lds_bytes(node_cap, scan_cap) + (size_t)kc * (4 + (u8 ? 1 : 2));
+    const size_t lds = dist_node_bytes(node_cap, scan_cap) + dist_key_bytes(kc, u8);
     const int xcd = B % 8 == 0 ? 1 : 0;
     if (u8)
         return dispatch(k_distribute<uint8_t>, dim3(nlv * B), dim3(kDistThreads), lds, st, cell_count, cell_slots,

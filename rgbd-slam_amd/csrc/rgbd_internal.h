@@ -51,7 +51,7 @@ struct LevelCfg {
     float scale;               // mvScaleFactor[level]
     float size;                // (float)(int)(PATCH_SIZE * scale) (:680)
     int32_t key_off;           // offset of this level's candidate region in a frame's key scratch
-    int32_t key_cap;           // capacity of that region (sum of its cells' slot capacity)
+    int32_t key_cap;           // capacity of that region (sum of its cells' slot capacity, up to a multiple of 4)
     int32_t sel_off;           // offset of this level's selected-keypoint slots (per frame)
     int32_t rsx_off, rsy_off;  // resize tables (level l from l-1): x entries / y entries
     int32_t rs_xmax;           // first dx whose tap sx+1 falls outside the source row
