@@ -5,7 +5,7 @@
 //   rgbd::Extractor      <- Extractor(detector, descriptor, mode): (ORB2, ORB2) or (SVO, BRIEF), NORMAL
 //                           (main.cpp:31's default)                       Features/Extractor.h:9-72
 //   rgbd::Frame          <- Frame (keys, keysUn, descriptors, keys3Dc, outlier flags, pose)  Core/Frame.h
-//   rgbd::Matcher        <- Matcher::match                                Features/Matcher.h:23-24
+//   rgbd::Matcher        <- Matcher::match, Matcher::projectionMatch      Features/Matcher.h:23-26
 //   rgbd::RansacSE3      <- RansacSE3::compute + rmse / mvInliers / mT21   Solver/SolverSE3.h:15-57
 //   rgbd::Gicp           <- Gicp::compute / align + setters                 Solver/Gicp.h:10-57
 //   rgbd::PnPRansac      <- PnPRansac::compute                             Solver/PnPRansac.h
@@ -14,7 +14,9 @@
 // matches are the byte-identical rgbd_keypoint / rgbd_dmatch.  INTEGRATION.md shows the thin
 // cv::Feature2D / cv::Mat adapters a maintainer adds on the reference side.
 #pragma once
+#include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -178,6 +180,50 @@ public:
         mDescriptors.resize((size_t)n * 32);
         mvKeys3Dc.resize((size_t)n * 3);
         mvbOutlier.assign(n, 0);
+        // computeImageBounds + the grid element sizes + assignFeaturesToGrid (Core/Frame.cpp:57-66, :75-89)
+        rgbd_bounds b{};
+        check(c, rgbd_image_bounds(c, &b), "image bounds");
+        mnMinX = b.min_x; mnMaxX = b.max_x; mnMinY = b.min_y; mnMaxY = b.max_y;
+        mfGridElementWidthInv = static_cast<float>(FRAME_GRID_COLS) / (mnMaxX - mnMinX);
+        mfGridElementHeightInv = static_cast<float>(FRAME_GRID_ROWS) / (mnMaxY - mnMinY);
+        mGrid.assign((size_t)FRAME_GRID_COLS * FRAME_GRID_ROWS, std::vector<size_t>());
+        for (int i = 0; i < N; i++) {
+            int gx, gy;
+            if (posInGrid(mvKeysUn[i], gx, gy)) mGrid[(size_t)gx * FRAME_GRID_ROWS + gy].push_back((size_t)i);
+        }
+    }
+    // Frame::posInGrid (Core/Frame.cpp:231-241); a keypoint outside the grid is in no cell
+    bool posInGrid(const rgbd_keypoint& kp, int& posX, int& posY) const
+    {
+        const float fx = std::round((kp.x - mnMinX) * mfGridElementWidthInv);
+        const float fy = std::round((kp.y - mnMinY) * mfGridElementHeightInv);
+        if (!(fx >= 0.0f && fx < (float)FRAME_GRID_COLS && fy >= 0.0f && fy < (float)FRAME_GRID_ROWS)) return false;
+        posX = (int)fx;
+        posY = (int)fy;
+        return true;
+    }
+    // Frame::getFeaturesInArea (Core/Frame.cpp:179-229), host code over mGrid; levels are checked when
+    // minLevel > 0 || maxLevel >= 0, as in the reference
+    std::vector<size_t> getFeaturesInArea(float x, float y, float r, int minLevel = -1, int maxLevel = -1) const
+    {
+        std::vector<size_t> vIndices;
+        const float c0 = std::floor((x - mnMinX - r) * mfGridElementWidthInv), c1 = std::ceil((x - mnMinX + r) * mfGridElementWidthInv);
+        const float r0 = std::floor((y - mnMinY - r) * mfGridElementHeightInv), r1 = std::ceil((y - mnMinY + r) * mfGridElementHeightInv);
+        if (!(c0 < (float)FRAME_GRID_COLS) || !(c1 >= 0.0f) || !(r0 < (float)FRAME_GRID_ROWS) || !(r1 >= 0.0f)) return vIndices;
+        const int nMinCellX = c0 > 0.0f ? (int)c0 : 0, nMaxCellX = c1 < (float)(FRAME_GRID_COLS - 1) ? (int)c1 : FRAME_GRID_COLS - 1;
+        const int nMinCellY = r0 > 0.0f ? (int)r0 : 0, nMaxCellY = r1 < (float)(FRAME_GRID_ROWS - 1) ? (int)r1 : FRAME_GRID_ROWS - 1;
+        const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
+        for (int ix = nMinCellX; ix <= nMaxCellX; ix++)
+            for (int iy = nMinCellY; iy <= nMaxCellY; iy++)
+                for (size_t j : mGrid[(size_t)ix * FRAME_GRID_ROWS + iy]) {
+                    const rgbd_keypoint& kpUn = mvKeysUn[j];
+                    if (bCheckLevels) {
+                        if (kpUn.octave < minLevel) continue;
+                        if (maxLevel >= 0 && kpUn.octave > maxLevel) continue;
+                    }
+                    if (std::fabs(kpUn.x - x) < r && std::fabs(kpUn.y - y) < r) vIndices.push_back(j);
+                }
+        return vIndices;
     }
     bool isValidObs(size_t i) const { return mvKeys3Dc[3 * i + 2] > 0; }      // Core/Frame.cpp:415-418
     bool isOutlier(size_t i) const { return mvbOutlier[i] != 0; }
@@ -190,7 +236,11 @@ public:
         return z;
     }
 
+    static constexpr int FRAME_GRID_COLS = 64, FRAME_GRID_ROWS = 48;   // Core/Frame.h
     int N = 0;
+    float mnMinX = 0, mnMaxX = 0, mnMinY = 0, mnMaxY = 0;   // undistorted image bounds (computeImageBounds)
+    float mfGridElementWidthInv = 0, mfGridElementHeightInv = 0;
+    std::vector<std::vector<size_t>> mGrid;                 // mGrid[ix * FRAME_GRID_ROWS + iy], ascending indices
     double mTimeStamp = 0;
     rgbd_camera mCamera{};                  // mpCamera (RGBDcamera)
     std::vector<rgbd_keypoint> mvKeys, mvKeysUn;
@@ -213,6 +263,24 @@ public:
                                vMatches12.data(), (int)vMatches12.size(), &m), "match");
         vMatches12.resize(m);
         return m;
+    }
+    // Matcher::projectionMatch (Features/Matcher.cpp:35-104): F1's valid 3D points projected into F2 with the
+    // two frame poses, F2's keypoints within th pixels as candidates, assigned greedily in F1 order.  Like the
+    // reference it APPENDS to vMatches12, starts from an empty taken set and returns vMatches12.size().
+    int projectionMatch(const Frame& F1, const Frame& F2, std::vector<rgbd_dmatch>& vMatches12, float th = 5.0f)
+    {
+        const size_t n0 = vMatches12.size();
+        vMatches12.resize(n0 + (size_t)std::max(F1.N, 1));
+        const rgbd_bounds b{F2.mnMinX, F2.mnMaxX, F2.mnMinY, F2.mnMaxY};
+        int m = 0;
+        const rgbd_status s = rgbd_projection_match(ctx_, F1.mvKeys3Dc.data(), F1.mDescriptors.data(), F1.mvbOutlier.data(), F1.N,
+                                                    F1.getPose().data(), F2.mvKeysUn.data(), F2.mvKeys3Dc.data(),
+                                                    F2.mDescriptors.data(), F2.N, F2.getPose().data(), &b, th,
+                                                    vMatches12.data() + n0, F1.N, &m);
+        if (s != RGBD_OK) vMatches12.resize(n0);
+        check(ctx_, s, "projectionMatch");
+        vMatches12.resize(n0 + (size_t)m);
+        return (int)vMatches12.size();
     }
 
 private:

@@ -176,6 +176,45 @@ rgbd_status rgbd_match(rgbd_ctx* ctx, const uint8_t* desc_q, int32_t nq, const u
                        const uint8_t* outlier_q, const float* z_q, const float* z_t, float nnratio,
                        int32_t discard_outliers, rgbd_dmatch* out, int32_t cap, int32_t* m);
 
+/* Frame::computeImageBounds (Core/Frame.cpp:283-315): mnMinX, mnMaxX, mnMinY, mnMaxY.  k1 == 0: (0, W, 0, H);
+ * otherwise from the four image corners undistorted like keypoints (cv::undistortPoints, k_undistort's code). */
+typedef struct { float min_x, max_x, min_y, max_y; } rgbd_bounds;
+/* The context's bounds, computed on first use (one small launch for a distorted camera) and cached. */
+rgbd_status rgbd_image_bounds(rgbd_ctx* ctx, rgbd_bounds* out);
+
+/* Matcher::projectionMatch(F1, F2, vMatches12, th) (Features/Matcher.cpp:35-104, Features/Matcher.h:26) over
+ * Frame::unprojectWorld (Core/Frame.cpp:317-327), Frame::getFeaturesInArea with its default levels (-1, -1)
+ * (:179-229) and the 64 x 48 grid of assignFeaturesToGrid / posInGrid (:75-89, :231-241); the operator is the
+ * definition in DESIGN.md "Projection match definition".  F1: xyz1 = mvKeys3Dc (n1 x 3), desc1 (n1 x 32),
+ * outlier1 = mvbOutlier as u8 (NULL: none), Tcw1 = its pose (row-major 4x4).  F2: kps_un2 = mvKeysUn (x and y
+ * are read), xyz2 (z is read), desc2, Tcw2.  Camera = the context's; bounds NULL = the context's
+ * (rgbd_image_bounds).  th finite in [0, 65536], else RGBD_ERR_ARG; n2 > 65536: RGBD_ERR_UNSUPPORTED (the rank
+ * key holds a train position in 16 bits, as rgbd_knn2's).  Output in query order: {i1, i2, imgIdx -1 (the
+ * three-argument cv::DMatch constructor), (float)distance}; *m = the match count, also when it exceeds cap
+ * (RGBD_ERR_CAPACITY, the first cap matches written).  n1 == 0 or n2 == 0: RGBD_OK, *m = 0, nothing launched. */
+rgbd_status rgbd_projection_match(rgbd_ctx* ctx, const float* xyz1, const uint8_t* desc1, const uint8_t* outlier1,
+                                  int32_t n1, const float* Tcw1, const rgbd_keypoint* kps_un2, const float* xyz2,
+                                  const uint8_t* desc2, int32_t n2, const float* Tcw2, const rgbd_bounds* bounds,
+                                  float th, rgbd_dmatch* out, int32_t cap, int32_t* m);
+/* The same over P pairs (qframe[p], tframe[p]) of the frames of the context's last rgbd_extract_batch, all pairs
+ * in one pass (one workgroup chain per pair): poses = B x 16 Tcw (host), outlier = B x K u8 flags of the frames
+ * as queries (host) or NULL, K = rgbd_max_keypoints.  out: P x K (host), counts[P].  qframe[p] < 0 skips pair p
+ * (counts[p] = 0). */
+rgbd_status rgbd_projection_match_batch(rgbd_ctx* ctx, int32_t P, const int32_t* qframe, const int32_t* tframe,
+                                        const float* poses, const uint8_t* outlier, float th, rgbd_dmatch* out,
+                                        int32_t* counts);
+/* Parity hook, one pair with rgbd_projection_match's inputs: the geometry on its own, before the greedy
+ * assignment.  Per query i1: uv_bits[2 i1 ..] = the f32 bits of (u, v) (Features/Matcher.cpp:63-64; 0 where not
+ * computed: status 1-3); status[i1] = 0 searched, 1 outlier, 2 no depth, 3 behind the camera (invzc < 0), 4 out
+ * of the image bounds or NaN, 5 no cell range (getFeaturesInArea's early returns, Core/Frame.cpp:185-199);
+ * cand[i1 * cand_cap ..] = vIndices2 (:71) in visiting order, BEFORE the isValidObs and taken filters,
+ * cand_count[i1] = its length (the first cand_cap are written). */
+rgbd_status rgbd_debug_projection(rgbd_ctx* ctx, const float* xyz1, const uint8_t* desc1, const uint8_t* outlier1,
+                                  int32_t n1, const float* Tcw1, const rgbd_keypoint* kps_un2, const float* xyz2,
+                                  const uint8_t* desc2, int32_t n2, const float* Tcw2, const rgbd_bounds* bounds,
+                                  float th, uint32_t* uv_bits, int32_t* status, int32_t* cand, int32_t cand_cap,
+                                  int32_t* cand_count);
+
 /* ------------------------------------------------------------------ solvers */
 /* RansacSE3::compute (Solver/SolverSE3.cpp:23-133).  xyz1 = F1->mvKeys3Dc, xyz2 = F2->mvKeys3Dc
  * (N x 3 f32).  flags2 = F2->mvbOutlier (u8, updated when update_f2).  T21 row-major 4x4

@@ -6,6 +6,7 @@ that mirror the reference's operator surfaces for this path:
   ORBextractor.detect_and_compute  <- Extractor::detectAndCompute  Features/Extractor.h:40
   Frame(bgr, depth, extractor)     <- Frame::Frame                 Core/Frame.cpp:34-73
   Matcher(nnratio).match(ref, cur) <- Matcher::match               Features/Matcher.cpp:106-139
+  Context.projection_match(...)    <- Matcher::projectionMatch     Features/Matcher.cpp:35-104
   RansacSE3(...).compute(F1, F2, m) <- RansacSE3::compute          Solver/SolverSE3.cpp:23-133
 
 The GPU library is mandatory: there is no CPU fallback.  Importing works without a GPU
@@ -107,6 +108,11 @@ def track_state(cap: int) -> TrackState:
     return ts
 
 
+class Bounds(C.Structure):
+    """rgbd_bounds: Frame::computeImageBounds' mnMinX, mnMaxX, mnMinY, mnMaxY."""
+    _fields_ = [(n, C.c_float) for n in ("min_x", "max_x", "min_y", "max_y")]
+
+
 class PnpParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reprojection_error", C.c_float), ("confidence", C.c_double),
                 ("min_matches", C.c_int32), ("flag_segments", C.c_int32)]
@@ -147,6 +153,12 @@ _SIGS = {
     "rgbd_debug_selected": (_i32, [_vp, _i32, _i32, _vp, _i32, _PI]),
     "rgbd_knn2": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "rgbd_match": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, C.c_float, _i32, _vp, _i32, _PI]),
+    "rgbd_image_bounds": (_i32, [_vp, C.POINTER(Bounds)]),
+    "rgbd_projection_match": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, C.POINTER(Bounds), C.c_float,
+                                     _vp, _i32, _PI]),
+    "rgbd_projection_match_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]),
+    "rgbd_debug_projection": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, C.POINTER(Bounds), C.c_float,
+                                     _vp, _vp, _vp, _i32, _vp]),
     "rgbd_ransac_se3": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(RansacParams), C.POINTER(Rng),
                                C.POINTER(Sticky), _i32, _vp, _vp, _vp, _PI, C.POINTER(C.c_float), _PI]),
     "rgbd_rng_seed": (None, [C.POINTER(Rng), C.c_uint32]),
@@ -412,6 +424,81 @@ class Context:
                                      _ptr(zt), nnratio, int(discard_outliers), _ptr(out), len(out), C.byref(m)),
                     "match")
         return out[:m.value].copy()
+
+    # --- projection-guided matching (Matcher::projectionMatch, Features/Matcher.cpp:35-104)
+    def image_bounds(self) -> Bounds:
+        """Frame::computeImageBounds (Core/Frame.cpp:283-315) for this context's camera and image size."""
+        b = Bounds()
+        self._check(lib().rgbd_image_bounds(self._h, C.byref(b)), "image_bounds")
+        return b
+
+    @staticmethod
+    def _projection_args(xyz1, desc1, outlier1, Tcw1, kps_un2, xyz2, desc2, Tcw2, bounds):
+        xyz1 = np.ascontiguousarray(xyz1, np.float32).reshape(-1, 3)
+        desc1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32)
+        kun2 = np.ascontiguousarray(kps_un2, KEYPOINT_DTYPE)
+        xyz2 = np.ascontiguousarray(xyz2, np.float32).reshape(-1, 3)
+        desc2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        if len(desc1) != len(xyz1) or len(xyz2) != len(kun2) or len(desc2) != len(kun2):
+            raise ValueError("projection match: xyz / desc / keypoint lengths differ")
+        if outlier1 is not None:
+            outlier1 = np.ascontiguousarray(outlier1, np.uint8)
+            if len(outlier1) != len(xyz1):
+                raise ValueError("projection match: outlier1 length")
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        if bounds is not None and not isinstance(bounds, Bounds):
+            bounds = Bounds(*[float(v) for v in bounds])
+        keep = (xyz1, desc1, outlier1, T1, kun2, xyz2, desc2, T2, bounds)
+        args = [_ptr(xyz1), _ptr(desc1), _ptr(outlier1) if outlier1 is not None else None, len(xyz1), _ptr(T1), _ptr(kun2),
+                _ptr(xyz2), _ptr(desc2), len(kun2), _ptr(T2), C.byref(bounds) if bounds is not None else None]
+        return args, keep
+
+    def projection_match(self, xyz1, desc1, outlier1, Tcw1, kps_un2, xyz2, desc2, Tcw2, th=5.0, bounds=None, cap=None):
+        """Matcher::projectionMatch(F1, F2, matches, th) (rgbd_projection_match): F1 = (mvKeys3Dc, descriptors,
+        mvbOutlier or None, Tcw), F2 = (mvKeysUn, mvKeys3Dc, descriptors, Tcw); bounds None = image_bounds().
+        Matches in query order as DMATCH_DTYPE (imgIdx -1)."""
+        args, keep = self._projection_args(xyz1, desc1, outlier1, Tcw1, kps_un2, xyz2, desc2, Tcw2, bounds)
+        cap = len(keep[0]) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        m = C.c_int32(0)
+        self._check(lib().rgbd_projection_match(self._h, *args, float(th), _ptr(out), cap, C.byref(m)), "projection_match")
+        return out[:m.value].copy()
+
+    def projection_match_batch(self, qframe, tframe, poses, th=5.0, outlier=None):
+        """rgbd_projection_match_batch over the frames of the last extract_batch: pairs (qframe[p], tframe[p])
+        (qframe < 0 skips a pair), poses (B, 4, 4) Tcw, outlier (B, kp_cap) u8 or None.  A list of P match arrays."""
+        qf = np.ascontiguousarray(qframe, np.int32)
+        tf = np.ascontiguousarray(tframe, np.int32)
+        if len(qf) != len(tf):
+            raise ValueError("projection_match_batch: qframe and tframe lengths differ")
+        P, K = len(qf), self.kp_cap
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        if outlier is not None:
+            outlier = np.ascontiguousarray(outlier, np.uint8)
+            if outlier.shape != (len(poses), K):
+                raise ValueError("projection_match_batch: outlier must be (B, kp_cap)")
+        out = np.zeros((max(P, 1), K), DMATCH_DTYPE)
+        counts = np.zeros(max(P, 1), np.int32)
+        self._check(lib().rgbd_projection_match_batch(self._h, P, _ptr(qf), _ptr(tf), _ptr(poses),
+                                                      _ptr(outlier) if outlier is not None else None, float(th),
+                                                      _ptr(out), _ptr(counts)), "projection_match_batch")
+        return [out[p, :counts[p]].copy() for p in range(P)]
+
+    def debug_projection(self, xyz1, desc1, outlier1, Tcw1, kps_un2, xyz2, desc2, Tcw2, th=5.0, bounds=None, cand_cap=64):
+        """The geometry of projection_match on its own (rgbd_debug_projection): dict(uv_bits (n1, 2) u32,
+        status (n1,), cand = list of candidate index arrays in visiting order before the z and taken filters,
+        cand_count (n1,))."""
+        args, keep = self._projection_args(xyz1, desc1, outlier1, Tcw1, kps_un2, xyz2, desc2, Tcw2, bounds)
+        n1 = len(keep[0])
+        uv = np.zeros((max(n1, 1), 2), np.uint32)
+        status = np.zeros(max(n1, 1), np.int32)
+        cand = np.zeros((max(n1, 1), max(cand_cap, 1)), np.int32)
+        cnt = np.zeros(max(n1, 1), np.int32)
+        self._check(lib().rgbd_debug_projection(self._h, *args, float(th), _ptr(uv), _ptr(status), _ptr(cand), int(cand_cap),
+                                                _ptr(cnt)), "debug_projection")
+        return dict(uv_bits=uv[:n1].copy(), status=status[:n1].copy(), cand_count=cnt[:n1].copy(),
+                    cand=[cand[i, :min(cnt[i], cand_cap)].copy() for i in range(n1)])
 
     # --- solvers
     def ransac_se3(self, xyz1, xyz2, matches, prm: RansacParams, r: Rng, st: Sticky, flags2=None):

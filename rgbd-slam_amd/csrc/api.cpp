@@ -735,6 +735,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::ransac_free(c);
     rgbd::gicp_free(c);
     rgbd::cloud_free(c);
+    rgbd::proj_free(c);
     rgbd::svo_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);

@@ -23,6 +23,7 @@
 #include "dispatch.h"
 
 #include "rgbd_internal.h"
+#include "undistort_dev.h"
 #include "wave_dev.h"
 
 namespace rgbd {
@@ -2201,26 +2202,7 @@ __global__ __launch_bounds__(kUndThreads) void k_undistort(const uint16_t* __res
     const int vi = (int)ky, ui = (int)kx;
     const uint16_t draw = depth ? depth[((size_t)b * cfg.H + vi) * cfg.W + ui] : (uint16_t)0;
     float ux = kx, uy = ky;
-    if (cfg.undistort) {
-        // cv::undistortPoints(..., P=K): 5 iterations in double (Core/Frame.cpp:270)
-        const double fx = cfg.fx, fy = cfg.fy, cx = cfg.cx, cy = cfg.cy;
-        const double k0 = cfg.k1, k1 = cfg.k2, k2 = cfg.p1, k3 = cfg.p2, k4 = cfg.k3;
-        const double ifx = 1. / fx, ify = 1. / fy;
-        double xx = kx, yy = ky;
-        xx = (xx - cx) * ifx;
-        yy = (yy - cy) * ify;
-        const double x0 = xx, y0 = yy;
-        for (int j = 0; j < 5; j++) {
-            const double r2 = xx * xx + yy * yy;
-            const double icdist = 1 / (1 + ((k4 * r2 + k1) * r2 + k0) * r2);
-            const double deltaX = 2 * k2 * xx * yy + k3 * (r2 + 2 * xx * xx);
-            const double deltaY = k2 * (r2 + 2 * yy * yy) + 2 * k3 * xx * yy;
-            xx = (x0 - deltaX) * icdist;
-            yy = (y0 - deltaY) * icdist;
-        }
-        ux = (float)(fx * xx + cx);
-        uy = (float)(fy * yy + cy);
-    }
+    if (cfg.undistort) undistort_point(cfg, kx, ky, &ux, &uy);   // cv::undistortPoints(..., P=K), undistort_dev.h
     float* KU = out_kun + o * 7;
     KU[0] = ux; KU[1] = uy;
 #pragma unroll

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "project_dev.h"
 #include "rgbd_internal.h"
 
 namespace rgbd {
@@ -33,6 +34,16 @@ hipError_t launch_debug_rank16(const uint8_t* flags, int rows, uint32_t* slots, 
 constexpr int kKnnMaxTrain = 65536;
 hipError_t launch_knn2(const uint8_t* desc, const int* counts, const int* qf, const int* tf, int kp_cap, int max_q,
                  int4* out, int npairs, hipStream_t st);
+
+// projection-guided matching (project.hip): the corners' undistortion, then per pair the train grid, the window
+// search of every query (max_q rows; debug: candidate lists too) and the greedy assignment
+hipError_t launch_proj_bounds(const ExtractCfg* d_cfg, float* out4, hipStream_t st);
+hipError_t launch_proj_grid(const ProjFrames& f, const ProjCfg& g, const ProjWork& w, int npairs, hipStream_t st);
+// max_q / max_t = the most queries / trains any pair can have (the sorted train set, then minq / taken, are
+// held in LDS when max_t lets them fit)
+hipError_t launch_proj_search(const ProjFrames& f, const ProjCfg& g, const ProjWork& w, int max_q, int max_t, int npairs,
+                              bool debug, hipStream_t st);
+hipError_t launch_proj_assign(const ProjFrames& f, const ProjCfg& g, const ProjWork& w, int max_t, int npairs, hipStream_t st);
 
 #ifdef RGBD_PNP_PROFILE
 void fast_prof_dump(hipStream_t st, int n_cells);   // profiling builds: k_fast stage cycles (frame 0)
