@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "blur_tab.h"
 #include "context.h"
 #include "launch.h"
 
@@ -107,6 +108,7 @@ struct HostGeom {
     std::vector<ResizeX> rsx;
     std::vector<ResizeY> rsy;
     std::vector<QuadX> qx;
+    std::vector<BlurLevelTab> blur_tab;   // the matrix-core blur's operand tables, one set per level it takes
 };
 
 // resize(INTER_LINEAR) tables of OpenCV 3.4 resize() for src (sw,sh) -> dst (dw,dh)
@@ -487,12 +489,14 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
     }
     // level blur threads: one per column quad of each 32-row strip of each level; inner quads (bytes
     // x - 4 .. x + 11 inside the row) first, edge quads after them
+    g.blur_tab.clear();
     {
-        int t = 0, e = 0;
+        int t = 0, e = 0, m = 0;
         for (int l = 0; l < kMaxLevels; l++) {
             C.blur_t0[l] = t;
             C.blur_e0[l] = e;
-            C.blur_tx[l] = C.blur_ex[l] = 0;
+            C.blur_m0[l] = m;
+            C.blur_tx[l] = C.blur_ex[l] = C.blur_mt[l] = C.blur_ms[l] = C.blur_tab_off[l] = 0;
             if (l >= nl) continue;
             const int w = C.lv[l].w, Q = (w + 3) / 4, ty = (C.lv[l].h + kBlurTH - 1) / kBlurTH;
             if (w < 16 || C.lv[l].h < 8) return fail(c, RGBD_ERR_UNSUPPORTED, "pyramid level smaller than 16x8");
@@ -500,11 +504,24 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
             C.blur_tx[l] = qe - 1;            // inner quads 1 .. qe - 1
             C.blur_ex[l] = 1 + (Q - qe);      // quad 0 and quads qe .. Q - 1
             if (C.pb_seg[l] > 0) continue;    // blurred inside k_pyramid: no blur threads
+            // levels of a multi-level pyramid that hold a 64-byte window and a 32-row block: 32 x 32 tiles on the
+            // matrix cores, one wave per 32-column strip of up to kBlurMS row blocks (the blocks spread evenly)
+            BlurLevelTab bt;
+            if (RGBD_BLUR_MFMA && nl > 1 && blur_tab_build(w, C.lv[l].h, C.lv[l].stride, bt)) {
+                const int nb = blur_tab_tiles(C.lv[l].h), strips = (nb + kBlurMS - 1) / kBlurMS;
+                C.blur_mt[l] = blur_tab_tiles(w);
+                C.blur_ms[l] = (nb + strips - 1) / strips;
+                C.blur_tab_off[l] = (int)(g.blur_tab.size() * sizeof(BlurLevelTab));
+                g.blur_tab.push_back(bt);
+                m += C.blur_mt[l] * ((nb + C.blur_ms[l] - 1) / C.blur_ms[l]);
+                continue;
+            }
             t += C.blur_tx[l] * ty;
             e += C.blur_ex[l] * ty;
         }
         C.blur_t0[kMaxLevels] = t;
         C.blur_e0[kMaxLevels] = e;
+        C.blur_m0[kMaxLevels] = m;
     }
     // camera
     const rgbd_camera& k = c->cam;
@@ -567,13 +584,13 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
     // k_fast launches (blur-only grid first), so per-dispatch counters give the blur's share of the launch
     if (getenv("RGBD_PROF_FAST_SPLIT")) {
         RGBD_TRY(c, launch_fast(c->d_pyr, c->d_cells, c->d_segs, 0, c->d_cfg, c->d_cellc, c->d_slots, B, st, c->d_blur,
-                    C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels]), "fast (blur blocks)");
+                    C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels], c->d_blur_tab, C.blur_m0[kMaxLevels]), "fast (blur blocks)");
         RGBD_TRY(c, launch_fast(c->d_pyr, c->d_cells, c->d_segs, (int)c->segs.size(), c->d_cfg, c->d_cellc, c->d_slots, B, st,
                     c->d_blur, 0), "fast (segments)");
     } else
 #endif
     RGBD_TRY(c, launch_fast(c->d_pyr, c->d_cells, c->d_segs, (int)c->segs.size(), c->d_cfg, c->d_cellc, c->d_slots, B, st, c->d_blur,
-                C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels]), "fast");
+                C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels], c->d_blur_tab, C.blur_m0[kMaxLevels]), "fast");
     timer_end(c, tk);
     // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
     if ((hs = hook(1))) return hs;
@@ -668,6 +685,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (!s) s = check_hip(c, c->d_rsx.alloc(g.rsx.size()), "rsx");
     if (!s) s = check_hip(c, c->d_qx.alloc(g.qx.size()), "resize quads");
     if (!s) s = check_hip(c, c->d_rsy.alloc(g.rsy.size()), "rsy");
+    if (!s) s = check_hip(c, c->d_blur_tab.alloc(g.blur_tab.size() * sizeof(BlurLevelTab)), "blur tables");
     if (!s) s = check_hip(c, c->d_pyr.alloc(B * C.frame_pyr_bytes + 64), "pyramid");
     if (!s) s = check_hip(c, c->d_blur.alloc(B * C.frame_pyr_bytes + 64), "blurred pyramid");
     if (!s) s = check_hip(c, c->d_cellc.alloc(B * C.n_cells), "cell counts");
@@ -694,6 +712,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (!s) s = check_hip(c, hipMemcpy(c->d_segs, c->segs.data(), c->segs.size() * sizeof(FastSeg), hipMemcpyHostToDevice), "upload segments");
     if (!s && !g.rsx.empty()) s = check_hip(c, hipMemcpy(c->d_rsx, g.rsx.data(), g.rsx.size() * sizeof(ResizeX), hipMemcpyHostToDevice), "upload rsx");
     if (!s && !g.qx.empty()) s = check_hip(c, hipMemcpy(c->d_qx, g.qx.data(), g.qx.size() * sizeof(QuadX), hipMemcpyHostToDevice), "upload quads");
+    if (!s && !g.blur_tab.empty()) s = check_hip(c, hipMemcpy(c->d_blur_tab, g.blur_tab.data(), g.blur_tab.size() * sizeof(BlurLevelTab), hipMemcpyHostToDevice), "upload blur tables");
     if (!s && !g.rsy.empty()) s = check_hip(c, hipMemcpy(c->d_rsy, g.rsy.data(), g.rsy.size() * sizeof(ResizeY), hipMemcpyHostToDevice), "upload rsy");
     if (!s) s = check_hip(c, hipMemset(c->d_err, 0, sizeof(int) * B), "memset err");
     if (!s) s = check_hip(c, hipMemset(c->d_pyr, 0, B * C.frame_pyr_bytes + 64), "memset pyr");

@@ -56,6 +56,7 @@ struct rgbd_ctx {
     rgbd::DevBuf<rgbd::ResizeX> d_rsx;
     rgbd::DevBuf<rgbd::ResizeY> d_rsy;
     rgbd::DevBuf<rgbd::QuadX> d_qx;
+    rgbd::DevBuf<uint8_t> d_blur_tab;          // operand tables of the level blur on the matrix cores (blur_tab.h)
     rgbd::DevBuf<uint8_t> d_pyr;
     rgbd::DevBuf<uint8_t> d_blur;              // blurred pyramid, same layout as d_pyr
     rgbd::DevBuf<int> d_cellc;

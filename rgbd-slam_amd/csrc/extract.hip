@@ -23,6 +23,7 @@
 #include "dispatch.h"
 
 #include "rgbd_internal.h"
+#include "blur_tab.h"
 #include "undistort_dev.h"
 #include "wave_dev.h"
 
@@ -682,6 +683,8 @@ __device__ __forceinline__ void row_pairs(uint32_t d0, uint32_t d1, uint32_t d2,
 #define RGBD_FAST_WPE 4   // waves per SIMD: 126 VGPRs for the exit-free 7-row walk blocks (at 5 waves, 96 VGPRs, they spill 48; r05 same-box A/B against 5 waves with per-row exits: +0.6 %, k_fast 1.67 -> 1.65 ms)
 __device__ __forceinline__ void blur_thread(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur,
                                             const ExtractCfg& cfg, int b, int t);
+__device__ __forceinline__ void blur_tile_walk(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, const uint8_t* __restrict__ tab,
+                               const ExtractCfg& cfg, int b, int wv);
 // k_fast's emission rank for 16-lane cells (one cell = one DPP row): corners below the lane over the whole
 // wave (pre), less those below the row (its lane 0's pre, row_newbcast:0) = the rank in the cell; the cell
 // total from its lane 15's inclusive count (row_newbcast:15).  cnt = the cell's next free slot (the same in
@@ -724,7 +727,8 @@ hipError_t launch_debug_rank16(const uint8_t* flags, int rows, uint32_t* slots, 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WPE, 8))) void k_fast(const uint8_t* __restrict__ pyr, const Cell* __restrict__ cells,
                                              const FastSeg* __restrict__ segs, const ExtractCfg* __restrict__ cfgp,
                                              int nseg, int* __restrict__ cell_count, uint32_t* __restrict__ cell_slots,
-                                             int xcd_map, uint8_t* __restrict__ blur, int nbb)
+                                             int xcd_map, uint8_t* __restrict__ blur, int nbb,
+                                             const uint8_t* __restrict__ blur_tab, int nbm)
 {
     const ExtractCfg& cfg = *cfgp;
     __shared__ __attribute__((aligned(16))) uint32_t roi[(kCellStride + 1) * kFastRowBytes / 4];   // + the walk's read-ahead row
@@ -732,7 +736,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
     // shared by neighbouring segments are fetched once into that XCD's L2.
     // nbb > 0: each frame's block sequence also holds the level blur's nbb 64-lane blocks (blur_thread,
     // levels RGBD_PB_LEVELS.. = 1-7) ahead of its segments, so blur and FAST waves share the CUs inside one launch instead
-    // of the blur competing from another stream with the quadtree
+    // of the blur competing from another stream with the quadtree; the first nbm of them are the tile waves of
+    // the levels blurred on the matrix cores (blur_tile_walk)
     const int n = nseg + nbb;
     int i = blockIdx.x, b = blockIdx.y;
     if (xcd_map) {
@@ -743,7 +748,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
     int si = i;
     if (nbb > 0) {
         if (i < nbb) {
-            blur_thread(pyr, blur, cfg, b, i * 64 + (int)threadIdx.x);
+            if (RGBD_BLUR_MFMA && i < nbm)
+                blur_tile_walk(pyr, blur, blur_tab, cfg, b, i);
+            else
+                blur_thread(pyr, blur, cfg, b, (i - nbm) * 64 + (int)threadIdx.x);
             return;
         }
         si = i - nbb;
@@ -1884,6 +1892,121 @@ __device__ __forceinline__ void blur_thread(const uint8_t* __restrict__ pyr, uin
     }
 }
 
+// The level blur of a 32-column strip on the matrix cores (RGBD_BLUR_MFMA; arithmetic, windows, slot maps and
+// tables: blur_tab.h, checked on the CPU by tests/blur_tab_check.cpp).  One wave walks blocks [j0, j1) of 32
+// output rows.  Per block it loads the next 32 x 64-byte input block (lane = row r, its 16 bytes from window
+// byte 16 hh and from 32 + 16 hh), forms the horizontal sums D = (p - 128) x Th (2 MFMAs: lane = column, 16
+// rows in registers) and splits them into the hi / lo byte fragments that are the vertical product's A operand
+// as they stand (the loads run one block ahead).  The vertical product takes the previous block's fragments (carried in 8 registers) and the
+// new ones against Tv, once for the hi and once for the lo bytes (4 MFMAs: lane = output row, registers = 4 x 4
+// consecutive columns, stored as one 16-byte piece per lane after a swap between the lane halves); out = byte 2 of 256 S_hi + S_lo + kBlurC.  So the operand packing is paid once per 1,024 output pixels and nothing crosses lanes.
+typedef int blur_v4i __attribute__((ext_vector_type(4)));
+typedef int blur_v4i_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef int blur_v16i __attribute__((ext_vector_type(16)));
+typedef unsigned short blur_u16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int blur_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ blur_u16x2 as_u16x2(uint32_t v) { return __builtin_bit_cast(blur_u16x2, v); }
+
+__device__ __forceinline__ void blur_tile_walk(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur,
+                                                         const uint8_t* __restrict__ tab, const ExtractCfg& cfg, int b, int wv)
+{
+    const int lane = (int)threadIdx.x, r = lane & 31, hh = lane >> 5;
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < kMaxLevels; i++) l += (i < cfg.nlevels && wv >= cfg.blur_m0[i]) ? 1 : 0;
+    const LevelCfg& L = cfg.lv[l];
+    const int nt = cfg.blur_mt[l], ms = cfg.blur_ms[l];
+    const int wl = wv - cfg.blur_m0[l];
+    const int strip = wl / nt, t = wl - strip * nt;
+    const int h = L.h, stride = L.stride;
+    const int nb = (h + 31) >> 5;
+    const int j0 = strip * ms, j1 = min(j0 + ms, nb);
+    const int c0 = min(max(32 * t - 4, 0), stride - 64);
+    const uint32_t fo = (uint32_t)b * (uint32_t)cfg.frame_pyr_bytes + (uint32_t)L.off;
+    // tables: [direction][index: first, interior, last two][MFMA][lane][16]
+    const uint8_t* ltab = tab + cfg.blur_tab_off[l] + lane * 16;
+    const uint8_t* th = ltab + blur_tab_index(t, nt) * 2048;
+    const blur_v4i th0 = *reinterpret_cast<const blur_v4i*>(th), th1 = *reinterpret_cast<const blur_v4i*>(th + 1024);
+    const uint32_t lbase = fo + (uint32_t)(c0 + 16 * hh);
+    auto load = [&](int i, blur_v4i& a0, blur_v4i& a1) {   // input block i: rows clamp(32 i - 4 + r, 0, h - 1)
+        const uint32_t o = lbase + (uint32_t)(min(max(32 * i - 4 + r, 0), h - 1) * stride);
+        a0 = *reinterpret_cast<const blur_v4i_a4*>(pyr + o);
+        a1 = *reinterpret_cast<const blur_v4i_a4*>(pyr + (o + 32u));
+    };
+    auto hsum = [&](blur_v4i a0, blur_v4i a1, blur_v4i& hi, blur_v4i& lo) {
+        a0 ^= (int)0x80808080u;
+        a1 ^= (int)0x80808080u;
+        blur_v16i d = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, th0, blur_v16i{}, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, th1, d, 0, 0, 0);
+#pragma unroll
+        for (int g = 0; g < 4; g++) {   // registers 4g .. 4g + 3 -> bytes 4g .. 4g + 3 of the fragments
+            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)d[4 * g + 1], (uint32_t)d[4 * g], 0x05040100u);
+            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)d[4 * g + 3], (uint32_t)d[4 * g + 2], 0x05040100u);
+            lo[g] = (int)(__builtin_amdgcn_perm(p23, p01, 0x06040200u) ^ 0x80808080u);
+            hi[g] = (int)__builtin_amdgcn_perm(p23, p01, 0x07050301u);
+        }
+    };
+    // Nothing a block loads is used by that block: its input rows and its vertical table were asked for one
+    // block earlier (without conditions: a walk's last block asks for its own again), and its stores have no
+    // condition either, so the wait for a block's operands is a count that leaves its predecessor's stores in
+    // flight.  The walk is written two blocks per loop turn with the operand sets swapping roles (A / B), so
+    // no register is copied from one block to the next; the warm-up waits for all it asked for, so the loop
+    // is entered with nothing pending.
+    const uint8_t* tvp = ltab + 4 * 2048;
+    auto load_tv = [&](int j, blur_v4i& t0, blur_v4i& t1) {
+        const uint8_t* tv = tvp + blur_tab_index(j, nb) * 2048;
+        t0 = *reinterpret_cast<const blur_v4i*>(tv);
+        t1 = *reinterpret_cast<const blur_v4i*>(tv + 1024);
+    };
+    const uint32_t sbase = fo + (uint32_t)(32 * t + 16 * hh);
+    struct Ops { blur_v4i a0, a1, tv0, tv1; };   // a block's input rows and vertical table
+    struct Frag { blur_v4i hi, lo; };            // a block's horizontal sums as the vertical A operand
+    auto block = [&](int j, const Ops& cur, Ops& nxt, const Frag& prev, Frag& mine) {
+        load(min(j + 2, j1), nxt.a0, nxt.a1);
+        load_tv(min(j + 1, j1 - 1), nxt.tv0, nxt.tv1);
+        hsum(cur.a0, cur.a1, mine.hi, mine.lo);
+        blur_v16i shi = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev.hi, cur.tv0, blur_v16i{}, 0, 0, 0);
+        blur_v16i slo = __builtin_amdgcn_mfma_i32_32x32x32_i8(prev.lo, cur.tv0, blur_v16i{}, 0, 0, 0);
+        shi = __builtin_amdgcn_mfma_i32_32x32x32_i8(mine.hi, cur.tv1, shi, 0, 0, 0);
+        slo = __builtin_amdgcn_mfma_i32_32x32x32_i8(mine.lo, cur.tv1, slo, 0, 0, 0);
+        // (rows past h - 1 compute row h - 1 again, blur_tab.h, and store it there: no condition on the stores)
+        const uint32_t so = sbase + (uint32_t)(min(32 * j + r, h - 1) * stride);
+        uint32_t o[4];   // columns 32 t + 8 g + 4 hh .. + 3 of the row
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            uint32_t x[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) x[i] = ((uint32_t)shi[4 * g + i] << 8) + (uint32_t)slo[4 * g + i];
+            // + kBlurC = 0x81 << 16 on the high halves, two per v_pk_add_u16 (only their low bytes are kept)
+            const blur_u16x2 q01 = as_u16x2(__builtin_amdgcn_perm(x[1], x[0], 0x07060302u)) + (unsigned short)(kBlurC >> 16);
+            const blur_u16x2 q23 = as_u16x2(__builtin_amdgcn_perm(x[3], x[2], 0x07060302u)) + (unsigned short)(kBlurC >> 16);
+            o[g] = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, q23), __builtin_bit_cast(uint32_t, q01), 0x06040200u);
+        }
+        // The two lanes of a row (hh = 0 / 1) hold alternate dwords of its 32 bytes.  Two v_permlane32_swap
+        // (o[0] <-> o[2], o[1] <-> o[3] between the lane halves) leave lane hh with the 16 consecutive bytes
+        // from column 32 t + 16 hh: one 16-byte store per lane, not four dword stores to 32 rows each.
+        // (bytes of a last tile past w land in the row padding)
+        const blur_u32x2 s02 = __builtin_amdgcn_permlane32_swap(o[0], o[2], false, false);
+        const blur_u32x2 s13 = __builtin_amdgcn_permlane32_swap(o[1], o[3], false, false);
+        *reinterpret_cast<blur_v4i_a4*>(blur + so) = blur_v4i{(int)s02[0], (int)s02[1], (int)s13[0], (int)s13[1]};
+    };
+    Ops A, B;
+    Frag fa, fb;
+    {
+        blur_v4i w0, w1;
+        load(j0, w0, w1);
+        load(j0 + 1, A.a0, A.a1);
+        load_tv(j0, A.tv0, A.tv1);
+        hsum(w0, w1, fb.hi, fb.lo);   // the warm-up block
+        asm volatile("" : "+v"(A.a0), "+v"(A.a1), "+v"(A.tv0), "+v"(A.tv1));   // (arrived: see above)
+    }
+    for (int j = j0; j < j1; j += 2) {
+        block(j, A, B, fb, fa);
+        if (j + 1 >= j1) break;
+        block(j + 1, B, A, fa, fb);
+    }
+}
+
 #define RGBD_DESC_WAVES 2   // waves per k_describe workgroup: 1 / 2 / 4 / 8 measured 134.1k / 134.2k / 132.1k / 126.1k frames/s at B = 512
 #define RGBD_DESC_EU 8   // min waves per SIMD: 64 VGPRs, so the 8 waves the LDS now allows fit (r04: 80 VGPRs held 6)
 constexpr int kDescWaves = RGBD_DESC_WAVES;
@@ -2244,17 +2367,19 @@ hipError_t launch_pyr_tail(uint8_t* pyr, const ResizeY* rsy, const QuadX* qx, co
 }
 
 hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* segs, int nseg, const ExtractCfg* d_cfg,
-                 int* cell_count, uint32_t* cell_slots, int B, hipStream_t st, uint8_t* blur, int blur_threads)
+                 int* cell_count, uint32_t* cell_slots, int B, hipStream_t st, uint8_t* blur, int blur_threads,
+                 const uint8_t* blur_tab, int blur_waves)
 {
-    // blur_threads > 0: the level blur's threads (per frame) as 64-lane blocks of the same grid (see k_fast)
-    const int nbb = blur_threads > 0 ? (blur_threads + 63) / 64 : 0;
+    // blur_waves tile waves (blur_tile_walk), then blur_threads > 0: the level blur's threads (per frame) as
+    // 64-lane blocks of the same grid (see k_fast)
+    const int nbb = blur_waves + (blur_threads > 0 ? (blur_threads + 63) / 64 : 0);
     // B a multiple of 8: 1-D grid of (nbb + nseg) * B single-wave blocks, frame b on XCD b % 8
     if (B % 8 == 0)
         return dispatch(k_fast, dim3((nbb + nseg) * B), dim3(64), 0, st, pyr, cells, segs, d_cfg, nseg, cell_count,
-                           cell_slots, 1, blur, nbb);
+                           cell_slots, 1, blur, nbb, blur_tab, blur_waves);
     else
         return dispatch(k_fast, dim3(nbb + nseg, B), dim3(64), 0, st, pyr, cells, segs, d_cfg, nseg, cell_count,
-                           cell_slots, 0, blur, nbb);
+                           cell_slots, 0, blur, nbb, blur_tab, blur_waves);
 }
 
 size_t distribute_lds_bytes(int NC, int SC)

@@ -13,7 +13,7 @@ hipError_t launch_pyramid(uint8_t* pyr, uint8_t* blur, const uint8_t* bgr, const
 hipError_t launch_pyr_tail(uint8_t* pyr, const ResizeY* rsy, const QuadX* qx, const ExtractCfg* d_cfg, int B, hipStream_t st);
 hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* segs, int nseg, const ExtractCfg* d_cfg,
                  int* cell_count, uint32_t* cell_slots, int B, hipStream_t st, uint8_t* blur = nullptr,
-                 int blur_threads = 0);
+                 int blur_threads = 0, const uint8_t* blur_tab = nullptr, int blur_waves = 0);
 // the quadtrees of levels [l0, l0 + nlv) of every frame; kc = LDS-resident keys per level
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,
                        int scan_cap, int l0, int nlv, int kc, uint32_t* keys, uint16_t* node, int* sel_count,

@@ -96,6 +96,14 @@ struct ExtractCfg {
     int32_t blur_tx[kMaxLevels];
     int32_t blur_e0[kMaxLevels + 1];
     int32_t blur_ex[kMaxLevels];
+    // level blur on the matrix cores (blur_tile_walk, RGBD_BLUR_MFMA): the levels it takes have no blur_thread
+    // threads; level l owns the waves [blur_m0[l], blur_m0[l + 1]) ahead of the blur_thread blocks, strip-major:
+    // blur_mt[l] 32-column tiles per strip of blur_ms[l] 32-row blocks; its tables (blur_tab.h) lie at byte
+    // blur_tab_off[l] of the table buffer
+    int32_t blur_m0[kMaxLevels + 1];
+    int32_t blur_mt[kMaxLevels];
+    int32_t blur_ms[kMaxLevels];
+    int32_t blur_tab_off[kMaxLevels];
     // k_pyramid's fused blur of the lowest levels (l < kPbLevels, multi-level pyramids): strip s blurs rows
     // [pb_r0, pb_r1) of level l (a partition of the level chosen inside the strips' overlaps, so the rows
     // +- 3 it reads are mostly computed for the next level anyway) in pb_seg[l] segments of kPbRows rows;
@@ -118,6 +126,20 @@ struct Cell {                  // one FAST ROI (rowRange/colRange of :655-660), 
 #ifndef RGBD_FAST_GATHER
 #define RGBD_FAST_GATHER 1
 #endif
+
+// k_fast's blur blocks, 0 / 1 for A/B builds: 1 = levels of at least 64 x 32 px of a multi-level pyramid are
+// blurred as 32 x 32 tiles on the matrix cores (blur_tile_walk), the smaller ones by blur_walk; 0 = blur_walk
+// for all (profiles/blur_mfma)
+#ifndef RGBD_BLUR_MFMA
+#define RGBD_BLUR_MFMA 1
+#endif
+// 32-row blocks a tile wave walks down its 32-column strip after one warm-up block of horizontal sums: 2 / 4 / 7 /
+// 13 (whole columns at 640 x 480) -> 3.927-3.963 / 3.843-3.872 / 3.796-3.844 / 3.790-3.794 ms per step against the
+// parent's 3.905-3.933 (profiles/blur_mfma/ab_ms.txt); taller levels spread their blocks evenly over strips
+#ifndef RGBD_BLUR_MS
+#define RGBD_BLUR_MS 13
+#endif
+constexpr int kBlurMS = RGBD_BLUR_MS;
 
 // k_fast's staged segment row.  A plain segment's cells lie side by side from a 16-B aligned start (<= 160 B);
 // a gathered segment gives each of its 64 / lpc slots kFastRowBytes / (64 / lpc) bytes (48 / 64 / 96), which
