@@ -18,6 +18,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -457,6 +458,74 @@ public:
 
     std::array<double, 9> R{};
     std::array<double, 3> t{};
+
+private:
+    rgbd_ctx* ctx_;
+    const Frame& F1_;
+    Frame& F2_;
+    const std::vector<rgbd_dmatch>& matches_;
+    bool as_written_;
+};
+
+// PnPSolver(F1, F2, matches).compute(inliers) (Solver/PnPSolver.cpp:31-150): motion-only bundle adjustment of
+// F2's pose from its current pose and the matches (rgbd_pnp_solver; DESIGN.md "Motion-only BA definition").
+// as_written = true keeps the reference's edges: Xw = F2's own unprojectWorld(trainIdx) under F2's current pose
+// (:65); the default pairs F1's unprojectWorld(queryIdx) under F1's pose with F2's pixels.  Every matched train
+// index is set inlier first (:68); after the solve F2's flags follow the outlier mask, F2's pose is the refined
+// one, and the inliers come back in ascending trainIdx order (the std::map iteration of :141-147), not in match
+// order.  Fewer than 3 matches: false, and the pose is left alone.
+// Precondition: the train indices are unique (Matcher::match and projectionMatch guarantee it) and the 3D points
+// used have z > 0.
+class PnPSolver {
+public:
+    PnPSolver(rgbd_ctx* ctx, const Frame& F1, Frame& F2, const std::vector<rgbd_dmatch>& matches, bool as_written = false)
+        : ctx_(ctx), F1_(F1), F2_(F2), matches_(matches), as_written_(as_written)
+    {
+    }
+    // Frame::unprojectWorld (Core/Frame.cpp:317-327) with updatePoseMatrices' float members: cv::Mat gemm, double
+    // accumulation, one rounding
+    static void unprojectWorld(const Pose& Tw, const float* x, float* xw)
+    {
+        for (int r = 0; r < 3; r++) {
+            double o = 0.0, a = 0.0;
+            for (int k = 0; k < 3; k++) {
+                o += (double)Tw[4 * k + r] * (double)Tw[4 * k + 3];
+                a += (double)Tw[4 * k + r] * (double)x[k];
+            }
+            const float Ow = (float)(o * -1.0);
+            xw[r] = (float)(a * 1.0 + (double)Ow * 1.0);
+        }
+    }
+    bool compute(std::vector<rgbd_dmatch>& inliers)
+    {
+        const int M = (int)matches_.size();
+        std::vector<float> Xw((size_t)std::max(M, 1) * 3), obs((size_t)std::max(M, 1) * 2);
+        for (int i = 0; i < M; i++) {
+            const rgbd_dmatch& m = matches_[i];
+            if (as_written_) unprojectWorld(F2_.getPose(), &F2_.mvKeys3Dc[3 * (size_t)m.trainIdx], &Xw[3 * (size_t)i]);
+            else unprojectWorld(F1_.getPose(), &F1_.mvKeys3Dc[3 * (size_t)m.queryIdx], &Xw[3 * (size_t)i]);
+            obs[2 * (size_t)i] = F2_.mvKeysUn[m.trainIdx].x;
+            obs[2 * (size_t)i + 1] = F2_.mvKeysUn[m.trainIdx].y;
+            F2_.mvbOutlier[m.trainIdx] = 0;
+        }
+        const float K4[4] = {F2_.mCamera.fx, F2_.mCamera.fy, F2_.mCamera.cx, F2_.mCamera.cy};
+        std::vector<uint8_t> mask((size_t)std::max(M, 1));
+        Pose T = identity();
+        int ninl = 0, ok = 0;
+        check(ctx_, rgbd_pnp_solver(ctx_, Xw.data(), obs.data(), M, K4, F2_.getPose().data(), nullptr, T.data(), mask.data(),
+                                    &ninl, &ok), "PnPSolver");
+        if (!ok) return false;
+        std::map<int, std::pair<rgbd_dmatch, bool>> matchesFlag;
+        for (int i = 0; i < M; i++) {
+            F2_.mvbOutlier[matches_[i].trainIdx] = mask[i];
+            matchesFlag[matches_[i].trainIdx] = {matches_[i], mask[i] == 0};
+        }
+        F2_.setPose(T);
+        inliers.clear();
+        for (const auto& kv : matchesFlag)
+            if (kv.second.second) inliers.push_back(kv.second.first);
+        return true;
+    }
 
 private:
     rgbd_ctx* ctx_;

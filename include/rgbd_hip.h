@@ -254,6 +254,55 @@ rgbd_status rgbd_pnp_ransac_batch(rgbd_ctx* ctx, int32_t P, const int32_t* count
                                   const float* K4, const rgbd_pnp_params* prm, double* R9, double* t3,
                                   uint8_t* masks, int32_t* n_inliers, int32_t* iters_run, int32_t* ok);
 
+/* PnPSolver::compute (Solver/PnPSolver.cpp:31-150): motion-only bundle adjustment of one pose from a guess and
+ * 3D-2D matches -- one g2o SE(3) vertex, one EdgeSE3ProjectXYZOnlyPose per match under a Huber kernel, `rounds`
+ * rounds of `iterations` Levenberg-Marquardt iterations, the edges reclassified against chi2_threshold between
+ * rounds.  g2o is absent; the operator is the definition in DESIGN.md "Motion-only BA definition", the
+ * reference's quirks included (every round restarts from the guess, an active edge is classified on the last
+ * error evaluated, fewer than min_edges edges run one round).  Parity against g2o is unpinned. */
+typedef struct {
+    int32_t rounds;          /* 4 */
+    int32_t iterations;      /* 10, per round */
+    double  chi2_threshold;  /* 5.991; Huber delta = sqrt of it */
+    int32_t robust_rounds;   /* 3: the kernel is removed after round index 2 */
+    int32_t min_edges;       /* 10: fewer edges -> only round 0 */
+} rgbd_pnp_solver_params;
+
+/* One problem: Xw M x 3 f32 (world points), obs M x 2 f32 (undistorted pixels), K4 = (fx, fy, cx, cy), Tcw_in
+ * the guess (row-major 4x4 float).  prm NULL = the reference's values above (rounds in [1, 16], iterations >= 1,
+ * chi2_threshold finite and > 0, else RGBD_ERR_ARG).  Out: Tcw_out (row-major 4x4 float), outlier_mask[M] u8 = 1
+ * where the edge ended flagged outlier, n_inliers, ok = the bool result: 0 for M < 3, and then nothing else is
+ * written.  M > 4096: RGBD_ERR_UNSUPPORTED before any copy or launch.  Inputs must be finite. */
+rgbd_status rgbd_pnp_solver(rgbd_ctx* ctx, const float* Xw, const float* obs, int32_t M, const float* K4,
+                            const float* Tcw_in, const rgbd_pnp_solver_params* prm, float* Tcw_out,
+                            uint8_t* outlier_mask, int32_t* n_inliers, int32_t* ok);
+/* P independent problems in one launch (one workgroup each): the edges of problem p follow those of p-1 in Xw /
+ * obs / masks; Tcw_in and Tcw_out [P][16], n_inliers / ok [P].  P = 0, or no problem with 3 edges: RGBD_OK and
+ * nothing launched. */
+rgbd_status rgbd_pnp_solver_batch(rgbd_ctx* ctx, int32_t P, const int32_t* counts, const float* Xw, const float* obs,
+                                  const float* K4, const float* Tcw_in, const rgbd_pnp_solver_params* prm,
+                                  float* Tcw_out, uint8_t* masks, int32_t* n_inliers, int32_t* ok);
+/* The same over P pairs (qframe[p], tframe[p]) of the frames of the context's last rgbd_extract_batch, reading
+ * rgbd_projection_match_batch's output as it stands: poses = B x 16 Tcw (host), matches = P x K (host), counts[P],
+ * K = rgbd_max_keypoints (<= 4096).  Edge i of pair p: obs = the train frame's mvKeysUn[trainIdx]; Xw =
+ * unprojectWorld(trainIdx) of the TRAIN frame under its own pose when as_written (Solver/PnPSolver.cpp:65), else
+ * unprojectWorld(queryIdx) of the query frame under its pose; the guess = poses[tframe[p]]; the camera = the
+ * context's.  masks: P x K by match position.  qframe[p] < 0 skips pair p (ok[p] = 0).  A match index outside
+ * [0, K): RGBD_ERR_ARG. */
+rgbd_status rgbd_pnp_solver_frames(rgbd_ctx* ctx, int32_t P, const int32_t* qframe, const int32_t* tframe,
+                                   const float* poses, const rgbd_dmatch* matches, const int32_t* counts,
+                                   int32_t as_written, const rgbd_pnp_solver_params* prm, float* Tcw_out,
+                                   uint8_t* masks, int32_t* n_inliers, int32_t* ok);
+/* Parity hook: rgbd_pnp_solver plus, per round r < rounds (zeros for a round not run; rounds_run = the rounds
+ * run): round_est[7 r ..] = the round's final estimate (qx qy qz qw tx ty tz), round_iters / round_trials = the
+ * LM iterations and trials run, round_lambda / round_nu = lambda and nu after the round; per round and edge
+ * edge_chi2[r M + i] = the chi2 the classification read and edge_level[r M + i] = the level it set. */
+rgbd_status rgbd_debug_pnp_solver(rgbd_ctx* ctx, const float* Xw, const float* obs, int32_t M, const float* K4,
+                                  const float* Tcw_in, const rgbd_pnp_solver_params* prm, float* Tcw_out,
+                                  uint8_t* outlier_mask, int32_t* n_inliers, int32_t* ok, int32_t* rounds_run,
+                                  double* round_est, int32_t* round_iters, int32_t* round_trials,
+                                  double* round_lambda, double* round_nu, double* edge_chi2, uint8_t* edge_level);
+
 /* Gicp (Solver/Gicp.cpp) over pcl::GeneralizedIterativeClosestPoint; Tracking sets max correspondence
  * distance 0.07 and 10 iterations (System/Tracking.cpp:147-151) on the ctor's 1e-9 transformation
  * epsilon (Solver/Gicp.cpp:12-15).  PCL is absent: DESIGN.md "GICP" defines the operator (PCL

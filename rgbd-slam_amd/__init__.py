@@ -7,6 +7,7 @@ that mirror the reference's operator surfaces for this path:
   Frame(bgr, depth, extractor)     <- Frame::Frame                 Core/Frame.cpp:34-73
   Matcher(nnratio).match(ref, cur) <- Matcher::match               Features/Matcher.cpp:106-139
   Context.projection_match(...)    <- Matcher::projectionMatch     Features/Matcher.cpp:35-104
+  Context.pnp_solver(...)          <- PnPSolver::compute           Solver/PnPSolver.cpp:31-150
   RansacSE3(...).compute(F1, F2, m) <- RansacSE3::compute          Solver/SolverSE3.cpp:23-133
 
 The GPU library is mandatory: there is no CPU fallback.  Importing works without a GPU
@@ -118,6 +119,12 @@ class PnpParams(C.Structure):
                 ("min_matches", C.c_int32), ("flag_segments", C.c_int32)]
 
 
+class PnpSolverParams(C.Structure):
+    """rgbd_pnp_solver_params: PnPSolver::compute's constants (Solver/PnPSolver.cpp:57, :102-132)."""
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32), ("chi2_threshold", C.c_double),
+                ("robust_rounds", C.c_int32), ("min_edges", C.c_int32)]
+
+
 class GicpParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("k_correspondences", C.c_int32), ("max_corr_dist", C.c_double),
                 ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
@@ -178,6 +185,12 @@ _SIGS = {
     "rgbd_pnp_track_batch": (_i32, [_vp, _vp, _vp, _i32, C.c_float, C.POINTER(PnpParams), _vp, _vp, _vp, _vp]),
     "rgbd_pnp_track_submit": (_i32, [_vp, _vp, _vp, _i32, C.c_float, C.POINTER(PnpParams)]),
     "rgbd_pnp_track_collect": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "rgbd_pnp_solver": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(PnpSolverParams), _vp, _vp, _PI, _PI]),
+    "rgbd_pnp_solver_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(PnpSolverParams), _vp, _vp, _vp, _vp]),
+    "rgbd_pnp_solver_frames": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, C.POINTER(PnpSolverParams), _vp, _vp, _vp,
+                                      _vp]),
+    "rgbd_debug_pnp_solver": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(PnpSolverParams), _vp, _vp, _PI, _PI, _PI,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rgbd_gicp": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI, _PI]),
     "rgbd_gicp_compute": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI]),
     "rgbd_set_tracking_gicp": (_i32, [_vp, C.POINTER(GicpParams)]),
@@ -262,6 +275,12 @@ def pnp_params(iters=500, reproj=3.0, conf=0.85, min_matches=10, flag_segments=0
     flag_segments (rgbd_pnp_track_*): 0 = independent pairs (discardOutliers = false); S >= 1 = the
     reference's outlier-flag chain over S contiguous runs of pairs (1 = one chain)."""
     return PnpParams(iters, reproj, conf, min_matches, flag_segments)
+
+
+def pnp_solver_params(rounds=4, iterations=10, chi2_threshold=5.991, robust_rounds=3, min_edges=10) -> PnpSolverParams:
+    """PnPSolver::compute's schedule: 4 rounds of 10 LM iterations, chi2 5.991 (Huber delta = its root), the kernel
+    removed after round index 2, fewer than 10 edges run one round (Solver/PnPSolver.cpp:57, :102-132)."""
+    return PnpSolverParams(rounds, iterations, chi2_threshold, robust_rounds, min_edges)
 
 
 def gicp_params(max_iterations=10, max_corr=0.07, gn_iterations=4, enable=True) -> GicpParams:
@@ -617,6 +636,116 @@ class Context:
         self._check(lib().rgbd_debug_rotation_ops(self._h, *[_ptr(a) for a in arrs], n, _ptr(sq), _ptr(q), _ptr(t)),
                     "debug_rotation_ops")
         return sq, q, t
+
+    # --- motion-only bundle adjustment (PnPSolver::compute, Solver/PnPSolver.cpp:31-150)
+    @staticmethod
+    def _pnp_solver_edges(Xw, obs, K4, Tcw_in):
+        Xw = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
+        obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 2)
+        if len(Xw) != len(obs):
+            raise ValueError("pnp_solver: Xw and obs lengths differ")
+        return Xw, obs, np.ascontiguousarray(K4, np.float32).reshape(4), np.ascontiguousarray(Tcw_in, np.float32).reshape(16)
+
+    def pnp_solver(self, Xw, obs, K4, Tcw_in, prm: PnpSolverParams | None = None):
+        """rgbd_pnp_solver: dict(ok, pose (4, 4) f32, mask (M,) u8 [1 = outlier], n_inliers); ok False (M < 3)
+        leaves the rest None.  prm None = the reference's values (NULL)."""
+        Xw, obs, K4, T = self._pnp_solver_edges(Xw, obs, K4, Tcw_in)
+        M = len(Xw)
+        pose = np.zeros(16, np.float32)
+        mask = np.zeros(max(M, 1), np.uint8)
+        ni, ok = C.c_int32(0), C.c_int32(0)
+        self._check(lib().rgbd_pnp_solver(self._h, _ptr(Xw), _ptr(obs), M, _ptr(K4), _ptr(T),
+                                          C.byref(prm) if prm is not None else None, _ptr(pose), _ptr(mask),
+                                          C.byref(ni), C.byref(ok)), "pnp_solver")
+        if not ok.value:
+            return dict(ok=False, pose=None, mask=None, n_inliers=None)
+        return dict(ok=True, pose=pose.reshape(4, 4), mask=mask[:M].copy(), n_inliers=ni.value)
+
+    def pnp_solver_batch(self, problems, K4, prm: PnpSolverParams | None = None):
+        """rgbd_pnp_solver_batch over problems = [(Xw, obs, Tcw_in), ...]: a list of pnp_solver's dicts."""
+        P = len(problems)
+        K4 = np.ascontiguousarray(K4, np.float32).reshape(4)
+        xs = [np.ascontiguousarray(p[0], np.float32).reshape(-1, 3) for p in problems]
+        os_ = [np.ascontiguousarray(p[1], np.float32).reshape(-1, 2) for p in problems]
+        if any(len(a) != len(b) for a, b in zip(xs, os_)):
+            raise ValueError("pnp_solver_batch: Xw and obs lengths differ")
+        counts = np.array([len(a) for a in xs], np.int32)
+        Xw = np.concatenate(xs + [np.zeros((0, 3), np.float32)])
+        obs = np.concatenate(os_ + [np.zeros((0, 2), np.float32)])
+        Tin = np.ascontiguousarray(np.stack([np.asarray(p[2], np.float32).reshape(16) for p in problems])
+                                   if P else np.zeros((0, 16)), np.float32)
+        pose = np.zeros((max(P, 1), 16), np.float32)
+        masks = np.zeros(max(int(counts.sum()), 1), np.uint8)
+        ni = np.zeros(max(P, 1), np.int32)
+        ok = np.zeros(max(P, 1), np.int32)
+        self._check(lib().rgbd_pnp_solver_batch(self._h, P, _ptr(counts), _ptr(Xw), _ptr(obs), _ptr(K4), _ptr(Tin),
+                                                C.byref(prm) if prm is not None else None, _ptr(pose), _ptr(masks),
+                                                _ptr(ni), _ptr(ok)), "pnp_solver_batch")
+        out, off = [], 0
+        for p in range(P):
+            if ok[p]:
+                out.append(dict(ok=True, pose=pose[p].reshape(4, 4).copy(), mask=masks[off:off + counts[p]].copy(),
+                                n_inliers=int(ni[p])))
+            else:
+                out.append(dict(ok=False, pose=None, mask=None, n_inliers=None))
+            off += int(counts[p])
+        return out
+
+    def pnp_solver_frames(self, qframe, tframe, poses, matches, as_written=False, prm: PnpSolverParams | None = None):
+        """rgbd_pnp_solver_frames over the frames of the last extract_batch: matches = projection_match_batch's
+        list of P match arrays (DMATCH_DTYPE), poses (B, 4, 4) Tcw.  A list of pnp_solver's dicts, the masks by
+        match position."""
+        qf = np.ascontiguousarray(qframe, np.int32)
+        tf = np.ascontiguousarray(tframe, np.int32)
+        P, K = len(qf), self.kp_cap
+        if len(tf) != P or len(matches) != P:
+            raise ValueError("pnp_solver_frames: qframe, tframe and matches lengths differ")
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        rows = np.zeros((max(P, 1), K), DMATCH_DTYPE)
+        counts = np.zeros(max(P, 1), np.int32)
+        for p, m in enumerate(matches):
+            if len(m) > K:
+                raise ValueError("pnp_solver_frames: more matches than kp_cap")
+            rows[p, :len(m)] = m
+            counts[p] = len(m)
+        pose = np.zeros((max(P, 1), 16), np.float32)
+        masks = np.zeros((max(P, 1), K), np.uint8)
+        ni = np.zeros(max(P, 1), np.int32)
+        ok = np.zeros(max(P, 1), np.int32)
+        self._check(lib().rgbd_pnp_solver_frames(self._h, P, _ptr(qf), _ptr(tf), _ptr(poses), _ptr(rows), _ptr(counts),
+                                                 int(bool(as_written)), C.byref(prm) if prm is not None else None,
+                                                 _ptr(pose), _ptr(masks), _ptr(ni), _ptr(ok)), "pnp_solver_frames")
+        return [dict(ok=True, pose=pose[p].reshape(4, 4).copy(), mask=masks[p, :counts[p]].copy(), n_inliers=int(ni[p]))
+                if ok[p] else dict(ok=False, pose=None, mask=None, n_inliers=None) for p in range(P)]
+
+    def debug_pnp_solver(self, Xw, obs, K4, Tcw_in, prm: PnpSolverParams | None = None):
+        """rgbd_debug_pnp_solver: pnp_solver's dict plus rounds_run and, per round, est (R, 7) f64 [q xyzw, t],
+        iters, trials, lam, nu (R,), chi2 (R, M) f64 and level (R, M) u8 (zeros for the rounds not run)."""
+        Xw, obs, K4, T = self._pnp_solver_edges(Xw, obs, K4, Tcw_in)
+        M = len(Xw)
+        R = prm.rounds if prm is not None else 4
+        if R < 1:
+            raise ValueError("debug_pnp_solver: rounds must be >= 1")
+        pose = np.zeros(16, np.float32)
+        mask = np.zeros(max(M, 1), np.uint8)
+        ni, ok, rr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        est = np.zeros((R, 7), np.float64)
+        iters, trials = np.zeros(R, np.int32), np.zeros(R, np.int32)
+        lam, nu = np.zeros(R, np.float64), np.zeros(R, np.float64)
+        chi2 = np.zeros((R, max(M, 1)), np.float64)
+        level = np.zeros((R, max(M, 1)), np.uint8)
+        self._check(lib().rgbd_debug_pnp_solver(self._h, _ptr(Xw), _ptr(obs), M, _ptr(K4), _ptr(T),
+                                                C.byref(prm) if prm is not None else None, _ptr(pose), _ptr(mask),
+                                                C.byref(ni), C.byref(ok), C.byref(rr), _ptr(est), _ptr(iters), _ptr(trials),
+                                                _ptr(lam), _ptr(nu), _ptr(chi2), _ptr(level)), "debug_pnp_solver")
+        # the device rows are M long
+        chi2 = chi2.reshape(-1)[:R * M].reshape(R, M) if M else chi2[:, :0]
+        level = level.reshape(-1)[:R * M].reshape(R, M) if M else level[:, :0]
+        out = dict(ok=bool(ok.value), rounds_run=rr.value, est=est, iters=iters, trials=trials, lam=lam, nu=nu,
+                   chi2=chi2.copy(), level=level.copy(), pose=None, mask=None, n_inliers=None)
+        if ok.value:
+            out.update(pose=pose.reshape(4, 4), mask=mask[:M].copy(), n_inliers=ni.value)
+        return out
 
     def pnp_ransac_batch(self, problems, K4, prm: PnpParams | None = None):
         """solvePnPRansac on each (p3 [n,3], p2 [n,2]) of `problems`; one pass for all of them.

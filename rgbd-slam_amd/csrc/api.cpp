@@ -755,6 +755,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::gicp_free(c);
     rgbd::cloud_free(c);
     rgbd::proj_free(c);
+    rgbd::pnpba_free(c);
     rgbd::svo_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
