@@ -535,4 +535,55 @@ private:
     bool as_written_;
 };
 
+// Ransac(F1, F2, matches, parameters).compute(inliers) (Solver/Ransac.cpp:12-59): the plain 3D-3D RANSAC on Umeyama
+// fits (rgbd_ransac_umeyama; DESIGN.md "Umeyama RANSAC definition").  The context and the Session (the process-global
+// rand() of the reference) come first, as with the other solvers here.  compute flags every matched train index of
+// F2 outlier and the final inliers' inlier, always sets F2's pose = inv(T) * pose(F1) (:53), and returns
+// !T.isIdentity(): a static camera returns false with its inliers set.  iterationCount is ignored, as in the
+// reference (:26); the reprojection and Mahalanobis versions throw (RGBD_ERR_UNSUPPORTED).
+class Ransac {
+public:
+    enum ERROR_VERSION { EUCLIDEAN_ERROR, REPROJECTION_ERROR, EUCLIDEAN_AND_REPROJECTION_ERROR, MAHALANOBIS_ERROR, ADAPTIVE_ERROR };
+    struct parameters {
+        int verbose;
+        int errorVersion, errorVersionVO, errorVersionMap;
+        double inlierThresholdEuclidean, inlierThresholdReprojection, inlierThresholdMahalanobis;
+        double minimalInlierRatioThreshold;
+        int minimalNumberOfMatches;
+        int usedPairs;
+        int iterationCount;
+    };
+    Ransac(rgbd_ctx* ctx, Session& s, const Frame& F1, Frame& F2, const std::vector<rgbd_dmatch>& matches, parameters params)
+        : ctx_(ctx), s_(s), F1_(F1), F2_(F2), matches_(matches),
+          prm_{params.errorVersion, params.usedPairs, params.minimalNumberOfMatches, 0, params.inlierThresholdEuclidean,
+               params.minimalInlierRatioThreshold}
+    {
+    }
+    bool compute(std::vector<rgbd_dmatch>& inliers)
+    {
+        const int M = (int)matches_.size();
+        inliers.resize((size_t)std::max(M, 1));
+        int n_in = 0, ok = 0;
+        check(ctx_, rgbd_ransac_umeyama(ctx_, F1_.mvKeys3Dc.data(), F1_.N, F2_.mvKeys3Dc.data(), F2_.N, matches_.data(), M, &prm_,
+                                        &s_.rng, F2_.mvbOutlier.data(), mT12.data(), inliers.data(), &n_in, &iterations, &ok),
+              "Ransac");
+        inliers.resize((size_t)n_in);
+        Pose P;
+        rgbd_ransac_umeyama_pose(mT12.data(), F1_.getPose().data(), P.data());
+        F2_.setPose(P);
+        return ok != 0;
+    }
+
+    Pose mT12 = identity();   // x1 = mT12 * x2: F2's camera points in F1's camera
+    int iterations = 0;       // RANSAC iterations run
+
+private:
+    rgbd_ctx* ctx_;
+    Session& s_;
+    const Frame& F1_;
+    Frame& F2_;
+    const std::vector<rgbd_dmatch>& matches_;
+    rgbd_umeyama_params prm_;
+};
+
 }  // namespace rgbd

@@ -303,6 +303,61 @@ rgbd_status rgbd_debug_pnp_solver(rgbd_ctx* ctx, const float* Xw, const float* o
                                   double* round_est, int32_t* round_iters, int32_t* round_trials,
                                   double* round_lambda, double* round_nu, double* edge_chi2, uint8_t* edge_level);
 
+/* Ransac::compute (Solver/Ransac.cpp:46-181): the plain 3D-3D RANSAC -- unweighted rigid Eigen::umeyama on
+ * used_pairs sampled matches, a Euclidean or depth-adaptive inlier test, an iteration count that adapts to the best
+ * inlier ratio, and a re-fit on the winner's inliers.  Eigen is absent; the operator is the definition in DESIGN.md
+ * "Umeyama RANSAC definition" (sequential f32 sums, the f32 JacobiSVD sweeps, a saturating iteration count).
+ * Parity against the reference binary is unpinned.  error_version follows Ransac::ERROR_VERSION: 0 EUCLIDEAN_ERROR,
+ * 4 ADAPTIVE_ERROR; 1, 2 (reprojection) and 3 (MAHALANOBIS_ERROR) are RGBD_ERR_UNSUPPORTED, as are used_pairs outside
+ * [3, 8], min_matches < used_pairs, min_inlier_ratio outside [0.05, 1] and more than 4096 matches, all before any
+ * copy or launch.  The parameters' iterationCount is ignored by the reference (:26) and has no field here. */
+typedef struct {
+    int32_t error_version;
+    int32_t used_pairs;          /* usedPairs */
+    int32_t min_matches;         /* minimalNumberOfMatches */
+    int32_t pad;
+    double  thr_euclidean;       /* inlierThresholdEuclidean (m; times the F1 point's z under ADAPTIVE_ERROR) */
+    double  min_inlier_ratio;    /* minimalInlierRatioThreshold */
+} rgbd_umeyama_params;
+
+/* One pair: xyz1 = F1->mvKeys3Dc (n1 x 3 f32), xyz2 = F2->mvKeys3Dc, m12 the matches (queryIdx into F1, trainIdx into
+ * F2; an index outside: RGBD_ERR_ARG).  rng in / out: glibc rand() after the last draw of the loop.  flags2 in / out =
+ * F2->mvbOutlier (n2 bytes): every match's trainIdx is set 1, then the final inliers' 0.  Out: T12 row-major 4x4
+ * (x1 = T12 x2: F2's camera points into F1's camera), inliers (capacity m) and n_inliers, iterations_run (RANSAC
+ * iterations, 0 when fewer than min_matches pass the depth gate), ok = !T12.isIdentity(1e-5), the bool result. */
+rgbd_status rgbd_ransac_umeyama(rgbd_ctx* ctx, const float* xyz1, int32_t n1, const float* xyz2, int32_t n2,
+                                const rgbd_dmatch* m12, int32_t m, const rgbd_umeyama_params* prm, rgbd_rng* rng,
+                                uint8_t* flags2, float* T12, rgbd_dmatch* inliers, int32_t* n_inliers,
+                                int32_t* iterations_run, int32_t* ok);
+/* P independent pairs in one launch (one workgroup each).  Pair p's clouds, flags, matches and inliers follow those
+ * of pair p - 1 in xyz1 (n1[p] rows), xyz2 and flags2 (n2[p]), m12 and inliers (counts[p]); rngs, T12 [P][16],
+ * n_inliers / iterations_run / ok [P].  P = 0: RGBD_OK and nothing launched. */
+rgbd_status rgbd_ransac_umeyama_batch(rgbd_ctx* ctx, int32_t P, const float* xyz1, const int32_t* n1, const float* xyz2,
+                                      const int32_t* n2, const rgbd_dmatch* m12, const int32_t* counts,
+                                      const rgbd_umeyama_params* prm, rgbd_rng* rngs, uint8_t* flags2, float* T12,
+                                      rgbd_dmatch* inliers, int32_t* n_inliers, int32_t* iterations_run, int32_t* ok);
+/* The same over P pairs (F1 = frame qframe[p], F2 = frame tframe[p]) of the context's last rgbd_extract_batch, the
+ * points read from the device-resident mvKeys3Dc.  matches, inliers and flags2 are P x K (host), K =
+ * rgbd_max_keypoints, counts[P].  qframe[p] < 0 skips pair p (identity, ok 0, its rng and flags untouched).  A frame
+ * or match index outside its range: RGBD_ERR_UNSUPPORTED. */
+rgbd_status rgbd_ransac_umeyama_frames(rgbd_ctx* ctx, int32_t P, const int32_t* qframe, const int32_t* tframe,
+                                       const rgbd_dmatch* matches, const int32_t* counts, const rgbd_umeyama_params* prm,
+                                       rgbd_rng* rngs, uint8_t* flags2, float* T12, rgbd_dmatch* inliers,
+                                       int32_t* n_inliers, int32_t* iterations_run, int32_t* ok);
+/* Parity hook: rgbd_ransac_umeyama plus, per evaluated hypothesis h < min(iterations_run, hyp_cap): hyp_pos[h
+ * used_pairs ..] = its sample (positions among the gated matches, in draw order), hyp_count[h] = its inliers (-1:
+ * the model failed), hyp_sneg[h] = 1 where Umeyama took S = (1, 1, -1); best_count = the inliers of the loop's best
+ * model; accepts[3 a ..] = (iteration, count, new bound) of acceptance a < min(n_accepts, accept_cap). */
+rgbd_status rgbd_debug_ransac_umeyama(rgbd_ctx* ctx, const float* xyz1, int32_t n1, const float* xyz2, int32_t n2,
+                                      const rgbd_dmatch* m12, int32_t m, const rgbd_umeyama_params* prm, rgbd_rng* rng,
+                                      uint8_t* flags2, float* T12, rgbd_dmatch* inliers, int32_t* n_inliers,
+                                      int32_t* iterations_run, int32_t* ok, int32_t hyp_cap, int32_t* hyp_pos,
+                                      int32_t* hyp_count, uint8_t* hyp_sneg, int32_t* best_count, int32_t accept_cap,
+                                      int32_t* accepts, int32_t* n_accepts);
+/* Host only: Tcw2 = inv(T12) * Tcw1 (:53), the inverse as DESIGN.md defines it (f32 Gaussian elimination with
+ * partial pivoting; cv::Mat::inv() itself is unpinned). */
+void rgbd_ransac_umeyama_pose(const float* T12, const float* Tcw1, float* Tcw2);
+
 /* Gicp (Solver/Gicp.cpp) over pcl::GeneralizedIterativeClosestPoint; Tracking sets max correspondence
  * distance 0.07 and 10 iterations (System/Tracking.cpp:147-151) on the ctor's 1e-9 transformation
  * epsilon (Solver/Gicp.cpp:12-15).  PCL is absent: DESIGN.md "GICP" defines the operator (PCL

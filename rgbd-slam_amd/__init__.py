@@ -8,6 +8,7 @@ that mirror the reference's operator surfaces for this path:
   Matcher(nnratio).match(ref, cur) <- Matcher::match               Features/Matcher.cpp:106-139
   Context.projection_match(...)    <- Matcher::projectionMatch     Features/Matcher.cpp:35-104
   Context.pnp_solver(...)          <- PnPSolver::compute           Solver/PnPSolver.cpp:31-150
+  Context.ransac_umeyama(...)      <- Ransac::compute              Solver/Ransac.cpp:46-181
   RansacSE3(...).compute(F1, F2, m) <- RansacSE3::compute          Solver/SolverSE3.cpp:23-133
 
 The GPU library is mandatory: there is no CPU fallback.  Importing works without a GPU
@@ -125,6 +126,12 @@ class PnpSolverParams(C.Structure):
                 ("robust_rounds", C.c_int32), ("min_edges", C.c_int32)]
 
 
+class UmeyamaParams(C.Structure):
+    """rgbd_umeyama_params: Ransac::parameters' fields that Ransac::compute reads (Solver/Ransac.h:21-29)."""
+    _fields_ = [("error_version", C.c_int32), ("used_pairs", C.c_int32), ("min_matches", C.c_int32), ("pad", C.c_int32),
+                ("thr_euclidean", C.c_double), ("min_inlier_ratio", C.c_double)]
+
+
 class GicpParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("k_correspondences", C.c_int32), ("max_corr_dist", C.c_double),
                 ("transformation_epsilon", C.c_double), ("rotation_epsilon", C.c_double),
@@ -191,6 +198,15 @@ _SIGS = {
                                       _vp]),
     "rgbd_debug_pnp_solver": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(PnpSolverParams), _vp, _vp, _PI, _PI, _PI,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbd_ransac_umeyama": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(UmeyamaParams), C.POINTER(Rng), _vp, _vp,
+                                   _vp, _PI, _PI, _PI]),
+    "rgbd_ransac_umeyama_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(UmeyamaParams), _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]),
+    "rgbd_ransac_umeyama_frames": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(UmeyamaParams), _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp]),
+    "rgbd_debug_ransac_umeyama": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(UmeyamaParams), C.POINTER(Rng), _vp,
+                                         _vp, _vp, _PI, _PI, _PI, _i32, _vp, _vp, _vp, _PI, _i32, _vp, _PI]),
+    "rgbd_ransac_umeyama_pose": (None, [_vp, _vp, _vp]),
     "rgbd_gicp": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI, _PI]),
     "rgbd_gicp_compute": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI]),
     "rgbd_set_tracking_gicp": (_i32, [_vp, C.POINTER(GicpParams)]),
@@ -281,6 +297,16 @@ def pnp_solver_params(rounds=4, iterations=10, chi2_threshold=5.991, robust_roun
     """PnPSolver::compute's schedule: 4 rounds of 10 LM iterations, chi2 5.991 (Huber delta = its root), the kernel
     removed after round index 2, fewer than 10 edges run one round (Solver/PnPSolver.cpp:57, :102-132)."""
     return PnpSolverParams(rounds, iterations, chi2_threshold, robust_rounds, min_edges)
+
+
+EUCLIDEAN_ERROR, REPROJECTION_ERROR, EUCLIDEAN_AND_REPROJECTION_ERROR, MAHALANOBIS_ERROR, ADAPTIVE_ERROR = range(5)
+
+
+def umeyama_params(error_version=EUCLIDEAN_ERROR, used_pairs=3, min_matches=10, thr=0.03,
+                   min_inlier_ratio=0.1) -> UmeyamaParams:
+    """Ransac::parameters (Solver/Ransac.h:21-29): errorVersion (Ransac::ERROR_VERSION), usedPairs,
+    minimalNumberOfMatches, inlierThresholdEuclidean, minimalInlierRatioThreshold."""
+    return UmeyamaParams(error_version, used_pairs, min_matches, 0, thr, min_inlier_ratio)
 
 
 def gicp_params(max_iterations=10, max_corr=0.07, gn_iterations=4, enable=True) -> GicpParams:
@@ -746,6 +772,123 @@ class Context:
         if ok.value:
             out.update(pose=pose.reshape(4, 4), mask=mask[:M].copy(), n_inliers=ni.value)
         return out
+
+    # --- Umeyama RANSAC (Ransac::compute, Solver/Ransac.cpp:46-181)
+    @staticmethod
+    def _um_result(T, inl, ni, it, ok, flags2, rng):
+        return dict(ok=bool(ok), T=np.array(T, np.float32).reshape(4, 4), inliers=inl[:ni].copy(), n_inliers=int(ni),
+                    iterations=int(it), flags2=flags2, rng=rng)
+
+    def ransac_umeyama(self, xyz1, xyz2, matches, prm: UmeyamaParams, rng: Rng, flags2=None, debug=False):
+        """rgbd_ransac_umeyama: dict(ok, T (4, 4) f32 [x1 = T x2], inliers (DMATCH_DTYPE), n_inliers, iterations,
+        flags2, rng).  rng is advanced in place; flags2 (F2's mvbOutlier, zeros when None) is updated in place.
+        debug: rgbd_debug_ransac_umeyama, adding hyp_pos (iterations, used_pairs), hyp_count, hyp_sneg, best_count
+        and accepts (n, 3) [iteration, count, new bound]."""
+        xyz1 = np.ascontiguousarray(xyz1, np.float32).reshape(-1, 3)
+        xyz2 = np.ascontiguousarray(xyz2, np.float32).reshape(-1, 3)
+        m = np.ascontiguousarray(matches, DMATCH_DTYPE)
+        M = len(m)
+        if flags2 is None:
+            flags2 = np.zeros(max(len(xyz2), 1), np.uint8)
+        if flags2.dtype != np.uint8 or not flags2.flags.c_contiguous or len(flags2) < len(xyz2):
+            raise ValueError("ransac_umeyama: flags2 must be a contiguous u8 array of F2's length")
+        T = np.zeros(16, np.float32)
+        inl = np.zeros(max(M, 1), DMATCH_DTYPE)
+        ni, it, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        head = (self._h, _ptr(xyz1), len(xyz1), _ptr(xyz2), len(xyz2), _ptr(m), M, C.byref(prm), C.byref(rng), _ptr(flags2),
+                _ptr(T), _ptr(inl), C.byref(ni), C.byref(it), C.byref(ok))
+        if not debug:
+            self._check(lib().rgbd_ransac_umeyama(*head), "ransac_umeyama")
+            return self._um_result(T, inl, ni.value, it.value, ok.value, flags2, rng)
+        cap = 31294 + 256   # iters(0.05), the largest count the limits allow, and a round
+        n = max(prm.used_pairs, 1)
+        pos = np.zeros((cap, n), np.int32)
+        cnt = np.zeros(cap, np.int32)
+        sneg = np.zeros(cap, np.uint8)
+        acc = np.zeros((4097, 3), np.int32)
+        best, nacc = C.c_int32(0), C.c_int32(0)
+        self._check(lib().rgbd_debug_ransac_umeyama(*head, cap, _ptr(pos), _ptr(cnt), _ptr(sneg), C.byref(best), 4097,
+                                                    _ptr(acc), C.byref(nacc)), "debug_ransac_umeyama")
+        out = self._um_result(T, inl, ni.value, it.value, ok.value, flags2, rng)
+        out.update(hyp_pos=pos[:it.value].copy(), hyp_count=cnt[:it.value].copy(), hyp_sneg=sneg[:it.value].copy(),
+                   best_count=best.value, accepts=acc[:nacc.value].copy())
+        return out
+
+    def ransac_umeyama_batch(self, problems, prm: UmeyamaParams, rngs):
+        """rgbd_ransac_umeyama_batch over problems = [(xyz1, xyz2, matches, flags2 or None), ...] and one Rng per
+        problem (advanced in place): a list of ransac_umeyama's dicts."""
+        P = len(problems)
+        if len(rngs) != P:
+            raise ValueError("ransac_umeyama_batch: one Rng per problem")
+        x1 = [np.ascontiguousarray(p[0], np.float32).reshape(-1, 3) for p in problems]
+        x2 = [np.ascontiguousarray(p[1], np.float32).reshape(-1, 3) for p in problems]
+        ms = [np.ascontiguousarray(p[2], DMATCH_DTYPE) for p in problems]
+        fl = [np.zeros(len(b), np.uint8) if p[3] is None else np.ascontiguousarray(p[3], np.uint8) for p, b in zip(problems, x2)]
+        n1 = np.array([len(a) for a in x1], np.int32)
+        n2 = np.array([len(a) for a in x2], np.int32)
+        counts = np.array([len(a) for a in ms], np.int32)
+        X1 = np.concatenate(x1 + [np.zeros((1, 3), np.float32)])
+        X2 = np.concatenate(x2 + [np.zeros((1, 3), np.float32)])
+        Mm = np.concatenate(ms + [np.zeros(1, DMATCH_DTYPE)])
+        Fl = np.concatenate(fl + [np.zeros(1, np.uint8)])
+        R = (Rng * max(P, 1))(*rngs)
+        T = np.zeros((max(P, 1), 16), np.float32)
+        inl = np.zeros(len(Mm), DMATCH_DTYPE)
+        ni, it, ok = (np.zeros(max(P, 1), np.int32) for _ in range(3))
+        self._check(lib().rgbd_ransac_umeyama_batch(self._h, P, _ptr(X1), _ptr(n1), _ptr(X2), _ptr(n2), _ptr(Mm), _ptr(counts),
+                                                    C.byref(prm), C.cast(R, _vp), _ptr(Fl), _ptr(T), _ptr(inl), _ptr(ni),
+                                                    _ptr(it), _ptr(ok)), "ransac_umeyama_batch")
+        out, om, o2 = [], 0, 0
+        for p in range(P):
+            C.memmove(C.byref(rngs[p]), C.byref(R[p]), C.sizeof(Rng))
+            f = Fl[o2:o2 + n2[p]].copy()
+            if problems[p][3] is not None:
+                problems[p][3][:] = f
+            out.append(self._um_result(T[p], inl[om:om + counts[p]], ni[p], it[p], ok[p], f, rngs[p]))
+            om += int(counts[p])
+            o2 += int(n2[p])
+        return out
+
+    def ransac_umeyama_frames(self, qframe, tframe, matches, prm: UmeyamaParams, rngs, flags2=None):
+        """rgbd_ransac_umeyama_frames over the frames of the last extract_batch: matches = a list of P match arrays
+        (DMATCH_DTYPE), one Rng per pair (advanced in place), flags2 (P, kp_cap) u8 or None (zeros).  A list of
+        ransac_umeyama's dicts (flags2 = the pair's kp_cap-long row)."""
+        qf = np.ascontiguousarray(qframe, np.int32)
+        tf = np.ascontiguousarray(tframe, np.int32)
+        P, K = len(qf), self.kp_cap
+        if len(tf) != P or len(matches) != P or len(rngs) != P:
+            raise ValueError("ransac_umeyama_frames: qframe, tframe, matches and rngs lengths differ")
+        rows = np.zeros((max(P, 1), K), DMATCH_DTYPE)
+        counts = np.zeros(max(P, 1), np.int32)
+        for p, m in enumerate(matches):
+            if len(m) > K:
+                raise ValueError("ransac_umeyama_frames: more matches than kp_cap")
+            rows[p, :len(m)] = m
+            counts[p] = len(m)
+        fl = np.zeros((max(P, 1), K), np.uint8) if flags2 is None else flags2
+        if fl.dtype != np.uint8 or not fl.flags.c_contiguous or fl.shape != (max(P, 1), K):
+            raise ValueError("ransac_umeyama_frames: flags2 must be (P, kp_cap) u8")
+        R = (Rng * max(P, 1))(*rngs)
+        T = np.zeros((max(P, 1), 16), np.float32)
+        inl = np.zeros((max(P, 1), K), DMATCH_DTYPE)
+        ni, it, ok = (np.zeros(max(P, 1), np.int32) for _ in range(3))
+        self._check(lib().rgbd_ransac_umeyama_frames(self._h, P, _ptr(qf), _ptr(tf), _ptr(rows), _ptr(counts), C.byref(prm),
+                                                     C.cast(R, _vp), _ptr(fl), _ptr(T), _ptr(inl), _ptr(ni), _ptr(it),
+                                                     _ptr(ok)), "ransac_umeyama_frames")
+        out = []
+        for p in range(P):
+            C.memmove(C.byref(rngs[p]), C.byref(R[p]), C.sizeof(Rng))
+            out.append(self._um_result(T[p], inl[p], ni[p], it[p], ok[p], fl[p], rngs[p]))
+        return out
+
+    @staticmethod
+    def ransac_umeyama_pose(T12, Tcw1):
+        """rgbd_ransac_umeyama_pose: inv(T12) * Tcw1 (Solver/Ransac.cpp:53), host only."""
+        a = np.ascontiguousarray(T12, np.float32).reshape(16)
+        b = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        out = np.zeros(16, np.float32)
+        lib().rgbd_ransac_umeyama_pose(_ptr(a), _ptr(b), _ptr(out))
+        return out.reshape(4, 4)
 
     def pnp_ransac_batch(self, problems, K4, prm: PnpParams | None = None):
         """solvePnPRansac on each (p3 [n,3], p2 [n,2]) of `problems`; one pass for all of them.
