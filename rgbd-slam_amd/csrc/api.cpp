@@ -166,7 +166,7 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
     std::memset(&C, 0, sizeof(C));
     const int nl = o.nlevels;
     if (nl < 1 || nl > kMaxLevels) return fail(c, RGBD_ERR_UNSUPPORTED, "nlevels must be in [1, 12]");
-    if (c->W % 16 != 0 || c->W <= 64 || c->H <= 64) return fail(c, RGBD_ERR_UNSUPPORTED, "width must be a multiple of 16 and > 64");
+    if (c->W % 16 != 0 || c->W < 64 || c->H <= 64) return fail(c, RGBD_ERR_UNSUPPORTED, "width must be a multiple of 16 and >= 64");
     if (c->W > 16 * kPyrThreads) return fail(c, RGBD_ERR_UNSUPPORTED, "width above 16 x the pyramid's threads per strip");
     C.W = c->W;
     C.H = c->H;
@@ -383,23 +383,15 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
         resize_tables(C.lv[l - 1].w, C.lv[l - 1].h, C.lv[l].w, C.lv[l].h, g, C.lv[l]);
     // k_pyramid strips (levels < pyr_top): each strip owns an equal share of every level's rows (written to HBM); walking
     // down from the top level, level l-1 must also hold the source rows (sy0, sy1) of the rows level l
-    // computes.  Levels l < Lf are also blurred in k_pyramid (GaussianBlur 7x7): the level is partitioned
-    // into blur rows [pb_r0, pb_r1) per strip with the boundaries in the middle of the neighbouring
-    // strips' overlap, and a strip's computed rows are widened to its blur rows +- 3 (REFLECT_101 rows
-    // at the image edges fall inside them).  The overlaps of the lowest levels already exceed 6 rows,
-    // so fusing them costs almost no extra resize work; the top levels' would cascade down the chain.
+    // computes.  The strips blur nothing (the level blur of every level runs inside the k_fast grid), so a
+    // strip's rows come from the resize alone.
     {
         size_t lds_a = 0, lds_b = 0;   // even / odd level strip buffers
-        const int Lf = nl > 1 ? std::min(kPbLevels, nl) : 0;
         const int top = std::min(nl, kPyrStripLevels);   // levels top .. nl-1: k_pyr_tail, no strip rows
         C.pyr_top = top;
         int r0[kPyrStrips][kMaxLevels], r1[kPyrStrips][kMaxLevels];
-        for (int l = 0; l < kMaxLevels; l++) C.pb_seg[l] = 0;
         for (int s_ = 0; s_ < kPyrStrips; s_++)
-            for (int l = 0; l < kMaxLevels; l++) {
-                C.strip_r0[s_][l] = C.strip_r1[s_][l] = 0;
-                C.pb_r0[s_][l] = C.pb_r1[s_][l] = 0;
-            }
+            for (int l = 0; l < kMaxLevels; l++) C.strip_r0[s_][l] = C.strip_r1[s_][l] = 0;
         for (int l = top - 1; l >= 0; l--) {
             const int h = C.lv[l].h;
             for (int s_ = 0; s_ < kPyrStrips; s_++) {
@@ -411,31 +403,7 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
                     r0[s_][l] = std::min(r0[s_][l], (int)a.sy0);
                     r1[s_][l] = std::max(r1[s_][l], (int)z.sy1 + 1);
                 }
-                C.pb_r0[s_][l] = C.pb_r1[s_][l] = 0;
             }
-            if (l >= Lf) continue;
-            int beta[kPyrStrips + 1];
-            beta[0] = 0;
-            beta[kPyrStrips] = h;
-            for (int s_ = 1; s_ < kPyrStrips; s_++)
-                beta[s_] = std::min(std::max((r0[s_][l] + r1[s_ - 1][l]) / 2, beta[s_ - 1]), h);
-            int maxrows = 0;
-            for (int s_ = 0; s_ < kPyrStrips; s_++) {
-                const int b0 = beta[s_], b1 = std::max(beta[s_ + 1], b0);
-                C.pb_r0[s_][l] = (int16_t)b0;
-                C.pb_r1[s_][l] = (int16_t)b1;
-                if (b1 <= b0) continue;
-                r0[s_][l] = std::min(r0[s_][l], std::max(b0 - 3, 0));
-                r1[s_][l] = std::max(r1[s_][l], std::min(b1 + 3, h));
-                maxrows = std::max(maxrows, b1 - b0);
-                // every row the blur reads (REFLECT_101) is computed by this strip
-                for (int y = b0 - 3; y < b1 + 3; y++) {
-                    const int ry = y < 0 ? -y : (y >= h ? 2 * h - 2 - y : y);
-                    if (ry < r0[s_][l] || ry >= r1[s_][l])
-                        return fail(c, RGBD_ERR_UNSUPPORTED, "fused blur row outside its pyramid strip");
-                }
-            }
-            C.pb_seg[l] = (maxrows + kPbRows - 1) / kPbRows;
         }
         for (int s_ = 0; s_ < kPyrStrips; s_++) {
             for (int l = 0; l < top; l++) {
@@ -503,9 +471,9 @@ rgbd_status build_geometry(rgbd_ctx* c, HostGeom& g)
             const int qe = (w - 8) / 4 + 1;   // first quad with 4q + 8 > w
             C.blur_tx[l] = qe - 1;            // inner quads 1 .. qe - 1
             C.blur_ex[l] = 1 + (Q - qe);      // quad 0 and quads qe .. Q - 1
-            if (C.pb_seg[l] > 0) continue;    // blurred inside k_pyramid: no blur threads
-            // levels of a multi-level pyramid that hold a 64-byte window and a 32-row block: 32 x 32 tiles on the
-            // matrix cores, one wave per 32-column strip of up to kBlurMS row blocks (the blocks spread evenly)
+            // levels of a multi-level pyramid (level 0 included) that hold a 64-byte window and a 32-row block:
+            // 32 x 32 tiles on the matrix cores, one wave per 32-column strip of up to kBlurMS row blocks; a taller
+            // level's nb blocks go to ceil(nb / kBlurMS) strips of near-equal length (15 at 480 rows: 8 + 7)
             BlurLevelTab bt;
             if (RGBD_BLUR_MFMA && nl > 1 && blur_tab_build(w, C.lv[l].h, C.lv[l].stride, bt)) {
                 const int nb = blur_tab_tiles(C.lv[l].h), strips = (nb + kBlurMS - 1) / kBlurMS;
@@ -560,7 +528,7 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
     int tk;
     if (C.nlevels > 1) {   // k_pyramid converts BGR -> gray (level 0) itself unless given a gray level 0
         tk = timer_begin(c, "k_pyramid");
-        RGBD_TRY(c, launch_pyramid(c->d_pyr, c->d_blur, from_gray ? nullptr : d_bgr, c->d_rsy, c->d_qx, c->d_cfg, C.pyr_lds + C.pyr_rsy_lds, B, st), "pyramid");
+        RGBD_TRY(c, launch_pyramid(c->d_pyr, from_gray ? nullptr : d_bgr, c->d_rsy, c->d_qx, c->d_cfg, C.pyr_lds + C.pyr_rsy_lds, B, st), "pyramid");
         timer_end(c, tk);
         if (C.pyr_top < C.nlevels) {   // the small levels after the strips
             tk = timer_begin(c, "k_pyr_tail");
@@ -575,9 +543,9 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
     auto hook = [&](int at) -> rgbd_status { return after_fast ? (*after_fast)(at) : RGBD_OK; };
     rgbd_status hs;
     if ((hs = hook(0))) return hs;
-    // the lowest levels' blur is fused into k_pyramid (blurred while the strip is in LDS); the others (all
-    // of a 1-level pyramid) are blurred by each frame's leading blocks of the k_fast grid (blur_thread), so
-    // blur and FAST waves share the CUs inside one launch
+    // every level is blurred by each frame's leading blocks of the k_fast grid (blur_tile_walk's tile waves,
+    // then blur_thread for the levels below the tile path's floor and for 1-level pyramids), so blur and FAST
+    // waves share the CUs inside one launch
     tk = timer_begin(c, "k_fast");
 #ifdef RGBD_PNP_PROFILE
     // profiling build: RGBD_PROF_FAST_SPLIT=1 dispatches the grid's blur blocks and its FAST segments as two

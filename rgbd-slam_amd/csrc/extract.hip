@@ -239,77 +239,6 @@ __device__ __forceinline__ int blur_edge_window(int x, int w, int* p, uint32_t* 
     return A;
 }
 
-// ------------------------------------------------------------------ fused level blur (k_pyramid)
-// GaussianBlur 7x7 (:745-746) of one level's strip while it is LDS-resident in k_pyramid (rows
-// [r0, r1) of the level, the strip's own rows +- 3 and every REFLECT_101 row they reach): item =
-// (segment of kPbRows own rows, column quad); the item walks its rows + 6 with a 7-row register window
-// of horizontal sums as row pairs (three LDS dwords and BlurCol::push per input row, BlurCol::out per output row).  Items
-// are dealt from the last thread down, so the threads the level's resize leaves idle take them first;
-// inner quads first, edge quads (REFLECT_101 columns) after them, so only one wave runs the v_perm path.
-template <bool kEdge, bool kLin>
-__device__ __forceinline__ void pb_walk(const uint8_t* lv, int r0, int r1, uint8_t* __restrict__ out, const LevelCfg& L,
-                                        int x, int ya, int yb)
-{
-    int p[3] = {0, 1, 2};
-    uint32_t sel[3] = {0x03020100u, 0x03020100u, 0x03020100u};
-    const int A = kEdge ? blur_edge_window(x, L.w, p, sel) : x - 4;
-    const uint8_t* base = lv + A;
-    const int h = L.h, nr = r1 - r0;
-    BlurCol col;
-#pragma unroll
-    for (int i = 0; i < kPbRows + 6; i++) {
-        int ro;
-        if (kLin) {   // every input row inside the strip and the level: consecutive LDS rows
-            ro = (ya - 3 - r0) * L.stride + i * L.stride;
-        } else {
-            int yi = ya - 3 + i;
-            yi = yi < 0 ? -yi : (yi >= h ? 2 * h - 2 - yi : yi);
-            yi = min(max(yi - r0, 0), nr - 1);   // rows past the segment's end feed outputs never stored
-            ro = __mul24(yi, L.stride);
-        }
-        const uint32_t* rp = reinterpret_cast<const uint32_t*>(base + ro);
-        uint32_t d[3];
-        if (kEdge) {
-            const uint32_t r[4] = {rp[0], rp[1], rp[2], rp[3]};
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const uint32_t lo = p[j] == 0 ? r[0] : (p[j] == 1 ? r[1] : r[2]);
-                const uint32_t hi = p[j] == 0 ? r[1] : (p[j] == 1 ? r[2] : r[3]);
-                d[j] = __builtin_amdgcn_perm(hi, lo, sel[j]);
-            }
-        } else {
-            d[0] = rp[0];
-            d[1] = rp[1];
-            d[2] = rp[2];
-        }
-        col.push(d[0], d[1], d[2]);
-        const int y = ya + i - 6;
-        if (i >= 6 && y < yb)   // bytes of a last quad past w land in the row padding
-            *reinterpret_cast<uint32_t*>(out + ((uint32_t)y * (uint32_t)L.stride + (uint32_t)x)) = col.out();
-    }
-}
-
-__device__ __forceinline__ void pyr_blur(const uint8_t* lv, const LevelCfg& L, int r0, int r1, uint8_t* __restrict__ out,
-                                         int o0, int o1, int nseg, int qin, int qex, int tid)
-{
-    const int nin = nseg * qin, ntot = nin + nseg * qex;
-    for (int i = kPyrThreads - 1 - tid; i < ntot; i += kPyrThreads) {
-        const bool edge = i >= nin;
-        const int j = edge ? i - nin : i, Q = edge ? qex : qin;
-        const int seg = (int)((unsigned)j / (unsigned)Q), qi = j - seg * Q;
-        const int ya = o0 + seg * kPbRows;
-        if (ya >= o1) continue;
-        const int yb = min(ya + kPbRows, o1);
-        const bool lin = ya - 3 >= max(r0, 0) && ya + kPbRows + 3 <= min(r1, L.h);
-        if (!edge) {
-            if (lin) pb_walk<false, true>(lv, r0, r1, out, L, 4 * (qi + 1), ya, yb);
-            else pb_walk<false, false>(lv, r0, r1, out, L, 4 * (qi + 1), ya, yb);
-        } else {   // x = 0, then the quads from the first with x + 8 > w
-            pb_walk<true, false>(lv, r0, r1, out, L, qi == 0 ? 0 : 4 * (qin + qi), ya, yb);
-        }
-    }
-}
-
 // One 4-px column quad of a resized row (cv::resize INTER_LINEAR, level l from l - 1) from the 12-byte
 // tap windows a (source row sy0) and c (sy1) at the quad's window base wb: the quad's host table QuadX
 // holds the window's byte shift, per-pixel v_perm selectors into it and packed x16 weights.
@@ -370,9 +299,15 @@ extern __device__ long long g_pyr_span[2048][2];
 #else
 #define PYR_PROF(k) do { } while (0)
 #endif
-__global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur,
-                                                         const uint8_t* __restrict__ bgr, const ResizeY* __restrict__ rsy,
-                                                         const QuadX* __restrict__ qxt, const ExtractCfg* __restrict__ cfgp)
+// Rows per thread whose level-0 loads are issued before the first conversion.  Without a blur halo a 640 x 480 strip
+// stages at most 35 rows, 12 per pass: 3 cover it (taller strips loop), and with 36 instead of 48 load registers live
+// the kernel takes 53 VGPRs instead of 67: 8 waves per SIMD, the four strip workgroups per CU its LDS now allows
+#ifndef RGBD_PYR_STAGE
+#define RGBD_PYR_STAGE 3
+#endif
+__global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t* __restrict__ pyr, const uint8_t* __restrict__ bgr,
+                                                         const ResizeY* __restrict__ rsy, const QuadX* __restrict__ qxt,
+                                                         const ExtractCfg* __restrict__ cfgp)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lbuf[];
     const ExtractCfg& cfg = *cfgp;
@@ -406,7 +341,7 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t* __restrict__ p
             };
             if (tr < RPS) {
                 // every task's loads first (one HBM round trip), then the conversions
-                constexpr int kStage = 4;
+                constexpr int kStage = RGBD_PYR_STAGE;
                 uint4 v[kStage][3];
 #pragma unroll
                 for (int u = 0; u < kStage; u++) {
@@ -488,20 +423,10 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(uint8_t* __restrict__ p
                 quad_row(QuadTaps(qxt + D.qx_off + q), q, r0 + yy, std::false_type{});
             }
         }
-        // the level blur of level l - 1 from its LDS strip (read-only in this phase)
-        if (cfg.pb_seg[l - 1] > 0)
-            pyr_blur(prev, S, cfg.strip_r0[st][l - 1], cfg.strip_r1[st][l - 1], blur + (size_t)b * cfg.frame_pyr_bytes + S.off,
-                     cfg.pb_r0[st][l - 1], cfg.pb_r1[st][l - 1], cfg.pb_seg[l - 1], cfg.blur_tx[l - 1], cfg.blur_ex[l - 1], tid);
         __syncthreads();
         PYR_PROF(1 + l);
         prev = cur;
         rs_cum += r1 - r0;
-    }
-    {
-        const int l = cfg.pyr_top - 1;
-        if (cfg.pb_seg[l] > 0)
-            pyr_blur(prev, cfg.lv[l], cfg.strip_r0[st][l], cfg.strip_r1[st][l], blur + (size_t)b * cfg.frame_pyr_bytes + cfg.lv[l].off,
-                     cfg.pb_r0[st][l], cfg.pb_r1[st][l], cfg.pb_seg[l], cfg.blur_tx[l], cfg.blur_ex[l], tid);
     }
 #ifdef RGBD_PNP_PROFILE
     if (tid == 0 && span_id < 2048) g_pyr_span[span_id][1] = wall_clock64();
@@ -734,8 +659,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
     __shared__ __attribute__((aligned(16))) uint32_t roi[(kCellStride + 1) * kFastRowBytes / 4];   // + the walk's read-ahead row
     // xcd_map (1-D grid, B a multiple of 8): all blocks of frame b run on XCD b % 8, in order, so the rows
     // shared by neighbouring segments are fetched once into that XCD's L2.
-    // nbb > 0: each frame's block sequence also holds the level blur's nbb 64-lane blocks (blur_thread,
-    // levels RGBD_PB_LEVELS.. = 1-7) ahead of its segments, so blur and FAST waves share the CUs inside one launch instead
+    // nbb > 0: each frame's block sequence also holds the level blur's nbb 64-lane blocks (every level)
+    // ahead of its segments, so blur and FAST waves share the CUs inside one launch instead
     // of the blur competing from another stream with the quadtree; the first nbm of them are the tile waves of
     // the levels blurred on the matrix cores (blur_tile_walk)
     const int n = nseg + nbb;
@@ -2355,10 +2280,10 @@ hipError_t launch_gray(const uint8_t* bgr, uint8_t* pyr, int W, int H, int frame
     return dispatch(k_gray, dim3(blocks), dim3(256), 0, st, bgr, pyr, W, H, frame_pyr_bytes, B);
 }
 
-hipError_t launch_pyramid(uint8_t* pyr, uint8_t* blur, const uint8_t* bgr, const ResizeY* rsy, const QuadX* qx, const ExtractCfg* d_cfg,
+hipError_t launch_pyramid(uint8_t* pyr, const uint8_t* bgr, const ResizeY* rsy, const QuadX* qx, const ExtractCfg* d_cfg,
                     int lds_bytes, int B, hipStream_t st)
 {
-    return dispatch(k_pyramid, dim3(kPyrStrips, B), dim3(kPyrThreads), lds_bytes, st, pyr, blur, bgr, rsy, qx, d_cfg);
+    return dispatch(k_pyramid, dim3(kPyrStrips, B), dim3(kPyrThreads), lds_bytes, st, pyr, bgr, rsy, qx, d_cfg);
 }
 
 hipError_t launch_pyr_tail(uint8_t* pyr, const ResizeY* rsy, const QuadX* qx, const ExtractCfg* d_cfg, int B, hipStream_t st)

@@ -19,14 +19,15 @@ constexpr int kPyrThreads = RGBD_PYR_THREADS;  // k_pyramid: threads per strip w
 #ifndef RGBD_PYR_STRIPS
 #define RGBD_PYR_STRIPS 16
 #endif
-constexpr int kPyrStrips = RGBD_PYR_STRIPS;  // k_pyramid: horizontal strips per frame (one workgroup each)
+constexpr int kPyrStrips = RGBD_PYR_STRIPS;  // k_pyramid: horizontal strips per frame (one workgroup each; 10 / 12 / 16 ->
+                                             // 3.685-3.697 / 3.695-3.701 / 3.664-3.669 ms per step: a 16th of 640 x 480 is
+                                             // 39 KB of LDS, four workgroups per CU, profiles/blur_level0)
 #define RGBD_BLUR_TH 48   // r04 (level blur of levels 1-7 in the k_fast grid): 16 / 32 / 48 rows -> 230.5k / 232.6k / 233.3k frames/s (profiles/r04_ab_blur_rows)
 constexpr int kBlurTH = RGBD_BLUR_TH;        // level blur: rows per strip (one thread per 4-px column quad)
-#define RGBD_PB_ROWS 7   // (sweep r03: 5 1.34 ms, 6 1.29, 7 1.21, 8 1.24, 10 1.32, 13 1.39, 16 1.38 k_pyramid)
-constexpr int kPbRows = RGBD_PB_ROWS;        // k_pyramid's fused level blur: output rows per (quad, segment) item
-#define RGBD_PB_LEVELS 1   // (r03 with kPbRows 7: 2 -> 202-203k frames/s, k_pyramid 1.07 ms; 3 -> 200k, 1.20 ms; 4 -> 182k;
-                           //  r04: 0 / 1 / 2 -> 232.2k / 232.7k / 230.8k, k_pyramid 0.82 / 0.95 / 1.07 ms, k_fast 1.83 / 1.69 / 1.60 ms)
-constexpr int kPbLevels = RGBD_PB_LEVELS;    // levels 0 .. kPbLevels-1 blurred inside k_pyramid, the rest inside k_fast's grid
+// bench.py's --full byte model (its PB_LEVELS, held to this line by tests/test_abi.py) charges the blurred bytes of
+// this many levels to k_pyramid.  No code reads it: k_pyramid blurs nothing since level 0 moved to k_fast's tile
+// waves, so that model's k_pyramid / k_fast figures are off by level 0's bytes ("Roofline accounting")
+#define RGBD_PB_LEVELS 1
 #ifndef RGBD_PYR_STRIP_LEVELS
 #define RGBD_PYR_STRIP_LEVELS 4
 #endif
@@ -38,7 +39,6 @@ constexpr int kPyrStripLevels = RGBD_PYR_STRIP_LEVELS;
 #define RGBD_PYR_TAIL_THREADS 256
 #endif
 constexpr int kPyrTailThreads = RGBD_PYR_TAIL_THREADS;   // k_pyr_tail: threads per frame workgroup (256 / 512 alike, ab25)
-static_assert(kPyrStripLevels > kPbLevels, "the strips must hold every level blurred inside k_pyramid");
 
 struct LevelCfg {
     int32_t w, h, stride;      // level image, row stride in the pyramid buffer
@@ -89,7 +89,7 @@ struct ExtractCfg {
     int32_t pyr_lds;           // bytes of LDS per strip workgroup: even levels at 0, odd levels at pyr_lds_b
     int32_t pyr_lds_b;
     int32_t pyr_rsy_lds;       // bytes of the strip's resize row entries, staged after the level buffers
-    // level blur (blur_thread): inner quads (x = 4 .. 4 * blur_tx[l]) of level l are threads [blur_t0[l], blur_t0[l + 1]),
+    // level blur of every level, inside the k_fast grid.  blur_thread: inner quads (x = 4 .. 4 * blur_tx[l]) of level l are threads [blur_t0[l], blur_t0[l + 1]),
     // strip-major; its edge quads (x = 0, then blur_ex[l] - 1 quads from 4 * (blur_tx[l] + 1)) are
     // threads blur_t0[kMaxLevels] + [blur_e0[l], blur_e0[l + 1])
     int32_t blur_t0[kMaxLevels + 1];
@@ -104,13 +104,6 @@ struct ExtractCfg {
     int32_t blur_mt[kMaxLevels];
     int32_t blur_ms[kMaxLevels];
     int32_t blur_tab_off[kMaxLevels];
-    // k_pyramid's fused blur of the lowest levels (l < kPbLevels, multi-level pyramids): strip s blurs rows
-    // [pb_r0, pb_r1) of level l (a partition of the level chosen inside the strips' overlaps, so the rows
-    // +- 3 it reads are mostly computed for the next level anyway) in pb_seg[l] segments of kPbRows rows;
-    // items = (segment, inner quad) then (segment, edge quad) with the quad sets of blur_tx / blur_ex.
-    // blur_thread (k_fast's leading blocks) covers the other levels (its ranges are empty for the fused ones).
-    int16_t pb_r0[kPyrStrips][kMaxLevels], pb_r1[kPyrStrips][kMaxLevels];
-    int32_t pb_seg[kMaxLevels];
     // k_describe: lv[l].sel_off for l < nlevels, INT32_MAX above (one contiguous scalar load; a slot's level is
     // the count of levels >= 1 whose first slot it has reached, with no nlevels test)
     int32_t sel_off_tab[kMaxLevels];
