@@ -128,6 +128,11 @@ rgbd_status rgbd_debug_candidates(rgbd_ctx* ctx, int32_t b, int32_t level, int32
                                   int32_t* n);
 rgbd_status rgbd_debug_selected(rgbd_ctx* ctx, int32_t b, int32_t level, int32_t* xys, int32_t cap,
                                 int32_t* n);
+/* How the last extraction's quadtree of (frame b, level) was run: 0 = per-key round state, 1 = count / best-key
+ * pyramids (no pass over the keys), 2 = the pyramid path abandoned for a node deeper than its bins (then the
+ * per-key state), 3 = the pyramid path skipped up front (a tree of too few keys to fill).  The selection is the
+ * same on every path. */
+rgbd_status rgbd_debug_dist_path(rgbd_ctx* ctx, int32_t b, int32_t level, int32_t* path);
 
 /* ------------------------------------------------------------------ SVO + BRIEF extractor */
 /* Extractor(SVO, BRIEF, NORMAL), the reference's default front end (main.cpp:31): SVOextractor(nlevels, 5,

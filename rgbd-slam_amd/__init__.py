@@ -165,6 +165,7 @@ _SIGS = {
     "rgbd_debug_blurred": (_i32, [_vp, _i32, _i32, _vp]),
     "rgbd_debug_candidates": (_i32, [_vp, _i32, _i32, _vp, _i32, _PI]),
     "rgbd_debug_selected": (_i32, [_vp, _i32, _i32, _vp, _i32, _PI]),
+    "rgbd_debug_dist_path": (_i32, [_vp, _i32, _i32, _PI]),
     "rgbd_knn2": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp]),
     "rgbd_match": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, C.c_float, _i32, _vp, _i32, _PI]),
     "rgbd_image_bounds": (_i32, [_vp, C.POINTER(Bounds)]),
@@ -448,6 +449,12 @@ class Context:
         n = C.c_int32(0)
         self._check(lib().rgbd_debug_selected(self._h, b, level, _ptr(out), cap, C.byref(n)), "debug_selected")
         return out[:n.value].copy()
+
+    def debug_dist_path(self, b: int, level: int) -> int:
+        """0 per-key state, 1 pyramid path, 2 pyramid path abandoned, 3 pyramid path skipped (rgbd_hip.h)."""
+        v = C.c_int32(-1)
+        self._check(lib().rgbd_debug_dist_path(self._h, b, level, C.byref(v)), "debug_dist_path")
+        return v.value
 
     # --- matching
     def knn2(self, dq: np.ndarray, dt: np.ndarray):

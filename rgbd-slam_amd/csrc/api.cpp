@@ -564,7 +564,7 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
     if ((hs = hook(1))) return hs;
     tk = timer_begin(c, "k_distribute");
     RGBD_TRY(c, launch_distribute(c->d_cellc, c->d_slots, c->d_cfg, C.node_cap, C.scan_cap, 0, C.nlevels, C.dist_kc, c->d_keys,
-                      c->d_node, c->d_selc, c->d_sel, c->d_err, B, st), "distribute");
+                      c->d_node, c->d_selc, c->d_sel, c->d_err, c->d_dist_path, B, st), "distribute");
     timer_end(c, tk);
     if ((hs = hook(2))) return hs;
 #ifdef RGBD_PNP_PROFILE
@@ -663,6 +663,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     // + kMaxLevels of slack: k_describe reads kMaxLevels counts from any frame's row unconditionally
     if (!s) s = check_hip(c, c->d_selc.alloc(sel_count_elems((int)B, C.nlevels)), "sel counts");
     if (!s) s = check_hip(c, c->d_sel.alloc(B * C.sel_per_frame), "sel");
+    if (!s) s = check_hip(c, c->d_dist_path.alloc(B * C.nlevels), "quadtree paths");
     if (!s) s = check_hip(c, c->own_out.count.alloc(B), "counts");
     if (!s) s = check_hip(c, c->own_out.kps.alloc(B * C.kp_cap * 7), "kps");
     if (!s) s = check_hip(c, c->own_out.kun.alloc(B * C.kp_cap * 7), "kps_un");
@@ -902,6 +903,18 @@ rgbd_status rgbd_debug_selected(rgbd_ctx* c, int32_t b, int32_t level, int32_t* 
     }
     if (n) *n = cnt;
     return cnt > cap ? fail(c, RGBD_ERR_CAPACITY, "capacity") : RGBD_OK;
+}
+
+rgbd_status rgbd_debug_dist_path(rgbd_ctx* c, int32_t b, int32_t level, int32_t* path)
+{
+    if (!c || !path || b < 0 || b >= c->maxB || level < 0 || level >= c->cfg.nlevels) return RGBD_ERR_ARG;
+    rgbd_status s = check_hip(c, hipStreamSynchronize(c->stream), "sync");
+    if (s) return s;
+    uint8_t v = 0;
+    s = check_hip(c, hipMemcpy(&v, c->d_dist_path + (size_t)b * c->cfg.nlevels + level, 1, hipMemcpyDeviceToHost),
+                  "read quadtree path");
+    *path = v;
+    return s;
 }
 
 // ------------------------------------------------------------------ matching

@@ -65,6 +65,7 @@ struct rgbd_ctx {
     rgbd::DevBuf<uint16_t> d_node;
     rgbd::DevBuf<int> d_selc;
     rgbd::DevBuf<uint32_t> d_sel;
+    rgbd::DevBuf<uint8_t> d_dist_path;         // k_distribute: the path of every (frame, level) tree (rgbd_debug_dist_path)
     rgbd::OutBufs own_out;               // the context's own output set; knn: [maxB][kp_cap]
     rgbd::OutSet out{};                  // the set the kernels read and write: own_out unless a pipelined
                                          // submission selected the second one (pnp_host.cpp)

@@ -1068,9 +1068,12 @@ __device__ int block_scan_excl(int* a, int n, int* wsum)
 #define RGBD_DIST_WPE 8
 // Where a level's per-round key state lives, chosen once per workgroup; each case runs its own instantiation of
 // the gather and key-pass bodies (as FastLg4 / FastLgN in k_fast), so no key loop tests the location per access.
-struct DistLL { static constexpr bool keysL = true, stateL = true; };     // keys and state in LDS
-struct DistGL { static constexpr bool keysL = false, stateL = true; };    // state in LDS, keys in the HBM scratch
-struct DistGG { static constexpr bool keysL = false, stateL = false; };   // both in the HBM scratch
+struct DistLL { static constexpr bool keysL = true, stateL = true, hist = false; };     // keys and state in LDS
+struct DistGL { static constexpr bool keysL = false, stateL = true, hist = false; };    // state in LDS, keys in the HBM scratch
+struct DistGG { static constexpr bool keysL = false, stateL = false, hist = false; };   // both in the HBM scratch
+struct DistHist { static constexpr bool keysL = false, stateL = false, hist = true; };  // pyramid path: no per-key state, no copy
+struct DistKeys { static constexpr bool pyr = false; };   // a round's child counts: from a pass over the keys ...
+struct DistPyr { static constexpr bool pyr = true; };     // ... or read from the count pyramid
 struct DistMid { static constexpr bool last = false; };
 struct DistLast { static constexpr bool last = true; };
 
@@ -1137,6 +1140,25 @@ __host__ __device__ constexpr size_t dist_node_bytes(int NC, int SC)
 // ... and of the key region for kc keys (kc a multiple of 16): the u32 keys + their state
 __host__ __device__ constexpr size_t dist_key_bytes(int kc, bool u8) { return (size_t)kc * 4 + (size_t)(kc >> 2) * (u8 ? 5 : 8); }
 
+// One-root levels, pyramid path.  quad_of and the child boxes split x and y separately, and a midpoint depends on
+// its own interval alone, so a node at depth d is a pair (ix, iy) of d-bit paths in two 1-D interval trees over
+// [0, rootX1] and [0, rootY1]: the tree's geometry does not depend on the keys.  The gather counts every key into
+// its depth-kDistD bin (two table reads) and maxes its best-key word there; both are then reduced up to depth 0,
+// and the division rounds read a child's size and its four child counts from the count pyramid, the last round
+// its nodes' best keys from the other: no pass over the keys and no per-key state.  Depth d is a 2^d x 2^d grid
+// (entry iy << d | ix) at dist_pyr_off(d).  kDistD = 5 (1024 bins, 2 x 1365 words in place of the key region): the
+// deepest node divided on 640 x 480 frames is at depth 3-4 at 1000 features; a round that would divide a node at
+// depth kDistD abandons the attempt (k_distribute).
+constexpr int kDistD = 5;
+__host__ __device__ constexpr int dist_pyr_off(int d) { return (int)(0x55555555u & ((1u << (2 * d)) - 1u)); }   // (4^d - 1) / 3
+constexpr int kDistPyrN = dist_pyr_off(kDistD + 1);
+static_assert(kDistPyrN == 1365 && dist_pyr_off(2) == 5, "pyramid offsets");
+// the two pyramids + the path tables of x = 0 .. rootX1 and y = 0 .. rootY1 (a byte each)
+__host__ __device__ constexpr size_t dist_hist_bytes(int rootX1, int rootY1)
+{
+    return (size_t)kDistPyrN * 8 + (size_t)(rootX1 + 1) + (size_t)(rootY1 + 1);
+}
+
 // NodeT: the per-key state's form in LDS (uint8_t: node-id and quadrant planes, while node_cap <= 256, i.e.
 // nfeatures <= ~1700; else uint16_t).
 // Levels [l0, l0 + nlv) of every frame, one workgroup each; kc = the keys per level whose round state (the
@@ -1149,7 +1171,8 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                                                              uint32_t* __restrict__ keys_g,
                                                              uint16_t* __restrict__ node_g,
                                                              int* __restrict__ sel_count, uint32_t* __restrict__ sel,
-                                                             int* __restrict__ err, int l0, int nlv, int kc, int xcd)
+                                                             int* __restrict__ err, uint8_t* __restrict__ path_out,
+                                                             int l0, int nlv, int kc, int xcd)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const ExtractCfg& cfg = *cfgp;
@@ -1206,13 +1229,16 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     const int nCells = LV.cell_count;
     const int nIni = LV.nIni;
     const float hX = LV.hX;
-    for (int i = tid; i < nCells; i += kDistThreads)
-        tmp[i] = cell_count[(size_t)b * cfg.n_cells + LV.cell_begin + i];
-    for (int i = tid; i < nIni; i += kDistThreads) sizeA[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < nCells; i += kDistThreads) tmp2[i] = tmp[i];
-    __syncthreads();
-    const int n = block_scan_excl(tmp2, nCells, wsum);   // tmp2 = offsets, tmp = counts
+    auto load_cells = [&]() __attribute__((always_inline)) {
+        for (int i = tid; i < nCells; i += kDistThreads)
+            tmp[i] = cell_count[(size_t)b * cfg.n_cells + LV.cell_begin + i];
+        for (int i = tid; i < nIni; i += kDistThreads) sizeA[i] = 0;
+        __syncthreads();
+        for (int i = tid; i < nCells; i += kDistThreads) tmp2[i] = tmp[i];
+        __syncthreads();
+        return block_scan_excl(tmp2, nCells, wsum);   // tmp2 = offsets, tmp = counts
+    };
+    const int n = load_cells();
     // Per-round key state: the key as FAST wrote it + its DistState.  Both in LDS when they fit (inL); else the
     // state alone in the same LDS region (ndL: the level's keys are written to the HBM scratch once by the gather
     // and only read after it, so no division round writes to HBM); else both in the HBM scratch
@@ -1253,7 +1279,27 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
     // gather itself counts every key's root quadrant and writes its first state (no root pass)
     const int rootX1 = (int)hX, rootY1 = LV.maxBY - LV.minBY;
     const int rootMx = (rootX1 + 1) >> 1, rootMy = (rootY1 + 1) >> 1;   // quad_of's midpoints of (0, 0, rootX1, rootY1)
-    if (nIni == 1) {
+    // pyramid path (see kDistD): the count and best-key pyramids and the two path tables lie in the key region
+    int* cntP = reinterpret_cast<int*>(kk32);
+    unsigned int* bestP = reinterpret_cast<unsigned int*>(cntP + kDistPyrN);
+    uint8_t* xcode = reinterpret_cast<uint8_t*>(bestP + kDistPyrN);
+    uint8_t* ycode = xcode + rootX1 + 1;
+    const int lane = tid & 63;
+    const unsigned long long lanes_below = (1ull << lane) - 1ull;
+    // the current node arrays (sz, cd, bx, cc) and the next round's; every tree starts on the B arrays
+    int* sz; int* cd; int16_t* bx; int* szN; int* cdN; int16_t* bxN; int* cc; int* ccN;
+    unsigned int* ubest = reinterpret_cast<unsigned int*>(best);
+    int L = 0, nextCid = nIni, phase = 1, rounds = 0;
+    bool best_done = false;
+    auto reset_lists = [&]() __attribute__((always_inline)) {
+        sz = sizeB; cd = cidB; bx = bxB;
+        szN = sizeA; cdN = cidA; bxN = bxA;
+        cc = childcnt; ccN = childcnt2;
+        nextCid = nIni; phase = 1; rounds = 0;
+        best_done = false;
+    };
+    reset_lists();
+    auto init_one_root = [&]() __attribute__((always_inline)) {
         if (tid == 0) {
             sizeB[0] = n;
             cidB[0] = 0;
@@ -1271,8 +1317,11 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
             }
         }
         __syncthreads();
-    }
-    with_loc([&](auto loc) __attribute__((always_inline)) {
+    };
+    // DistHist: every key counted into its depth-kDistD bin and its best-key word maxed there; the word's low bits
+    // are the key's slot in the level's cell lists (cell * cell_cap + j: the gather's key order, and where the
+    // selection reads the key back from), so nothing is copied
+    auto gather = [&](auto loc) __attribute__((always_inline)) {
         using Loc = decltype(loc);
         const auto st = state_of(loc);
         const int w = tid >> 6, sub = (tid >> 4) & 3, l16 = tid & 15;
@@ -1323,13 +1372,20 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                     } else {
                         v = src[j];
                     }
-                    if constexpr (Loc::keysL)
+                    if constexpr (Loc::hist) {
+                        // (a coordinate past the root box is on the far side of every midpoint, as rootX1 / rootY1 are)
+                        idx = ((int)ycode[min((int)((v >> 11) & 2047u), rootY1)] << kDistD) | (int)xcode[min((int)(v & 2047u), rootX1)];
+                        const int slot = (c00 + g * kCStep + sub) * cfg.cell_cap + j;
+                        atomicMax(&bestP[dist_pyr_off(kDistD) + idx], ((unsigned int)key_s(v) << 24) | (unsigned int)(0xFFFFFF - slot));
+                    } else if constexpr (Loc::keysL) {
                         kk32[o + j] = v;
-                    else
+                    } else {
                         keys[o + j] = v;
+                    }
                     // several roots: the key's root, counted into the root sizes; one root: the key's
                     // quadrant in the root box, counted into the first round's child counts
-                    if (nIni > 1) {
+                    if constexpr (Loc::hist) {
+                    } else if (nIni > 1) {
                         idx = (int)((float)(int)(v & 2047u) / hX);
                         idx = min(max(idx, 0), nIni - 1);
                         st.init_node(o + j, idx);
@@ -1338,21 +1394,23 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                         st.init_quad(o + j, idx);
                     }
                 }
-                lds_count(nIni > 1 ? sizeA : childcnt, idx, on && (nIni > 1 || n > 1));
+                if constexpr (Loc::hist)
+                    lds_count(cntP + dist_pyr_off(kDistD), idx, on);
+                else
+                    lds_count(nIni > 1 ? sizeA : childcnt, idx, on && (nIni > 1 || n > 1));
             }
             }
         }
-    });
+    };
+    // ---- the existing path's start: gather with the per-key state, then the roots
+    auto prepare_keys = [&]() __attribute__((always_inline)) {
+    if (nIni == 1) init_one_root();
+    with_loc(gather);
     __threadfence_block();
     __syncthreads();
     DIST_PROF(1);
 
     // ---- compaction of the non-empty roots (:448-459) on wave 0; current node arrays start as B
-    const int lane = tid & 63;
-    const unsigned long long lanes_below = (1ull << lane) - 1ull;
-    int* sz = sizeB; int* cd = cidB; int16_t* bx = bxB;
-    int* szN = sizeA; int* cdN = cidA; int16_t* bxN = bxA;
-    int* cc = childcnt; int* ccN = childcnt2;
     if (nIni > 1 && tid < 64) {
         int carry = 0;
         for (int base = 0; base < nIni; base += 64) {
@@ -1375,7 +1433,7 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
         if (lane == 0) s_J = carry;
     }
     if (nIni > 1) __syncthreads();   // (one root: s_J was set before the gather)
-    int L = s_J;
+    L = s_J;
     // several roots: root ids -> compacted ids, fused with the first round's child counts (four keys per thread
     // per step, the next step's keys loaded ahead, as in the division rounds below)
     if (nIni > 1) {
@@ -1403,18 +1461,18 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
         __threadfence_block();
         __syncthreads();
     }
+    };
 
-    DIST_PROF(2);
     // ---- division rounds.  Node bookkeeping (order, child offsets, survivors) runs on wave 0 with
     //      wave-level scans; the one pass over the keys per round moves every key to its new node
     //      and counts it into the new node's quadrant for the next round (or, in the last round,
-    //      into the best-key slot of its final node)
-    unsigned int* ubest = reinterpret_cast<unsigned int*>(best);
-    int nextCid = nIni;
-    int phase = 1;
-    int rounds = 0;
-    bool best_done = false;
-    __shared__ int s_round[4];   // T, Lnew, nToExpand, last
+    //      into the best-key slot of its final node).  DistPyr: no key pass; a node's box entries hold its
+    //      (depth, ix, iy), a fresh child's four child counts are read from the count pyramid and the last
+    //      round's best keys from the other.  It returns true, with nothing written outside LDS, when the round
+    //      would divide a node at depth kDistD, whose child counts the pyramid does not hold.
+    __shared__ int s_round[5];   // T, Lnew, nToExpand, last, (DistPyr) abandon
+    auto run_rounds = [&](auto mode) __attribute__((always_inline)) -> bool {
+    constexpr bool kPyr = decltype(mode)::pyr;
     while (L > 0 && rounds < 4096) {
         rounds++;
         const int prevSize = L;
@@ -1524,9 +1582,36 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                 sv += __popcll(bal);
             }
             // children, newest first
+            [[maybe_unused]] bool deep = false;   // (DistPyr) a node at depth kDistD is being divided
             for (int j = lane; j < nApply; j += 64) {
                 const int nd = ord[j];
                 int o = tmp[j];
+                if constexpr (kPyr) {
+                    const int d = bx[4 * nd], ix = bx[4 * nd + 1], iy = bx[4 * nd + 2];
+                    deep = deep || d >= kDistD;   // (its child counts are zeros: it gets no children here)
+                    for (int q = 0; q < 4; q++) {
+                        const int cnt = cc[4 * nd + q];
+                        if (cnt > 0) {
+                            const int ni = T - 1 - o;
+                            const int cdp = d + 1, cx = 2 * ix + (q & 1), cy = 2 * iy + (q >> 1);
+                            szN[ni] = cnt;
+                            cdN[ni] = nextCid + o;
+                            bxN[4 * ni + 0] = (int16_t)cdp;
+                            bxN[4 * ni + 1] = (int16_t)cx;
+                            bxN[4 * ni + 2] = (int16_t)cy;
+                            bxN[4 * ni + 3] = 0;
+                            int4 c4 = make_int4(0, 0, 0, 0);
+                            if (cnt > 1 && cdp < kDistD) {
+                                const int rw = 2 << cdp;   // row length of depth cdp + 1
+                                const int* gp = cntP + dist_pyr_off(cdp + 1) + 2 * cy * rw + 2 * cx;
+                                c4 = make_int4(gp[0], gp[1], gp[rw], gp[rw + 1]);
+                            }
+                            *reinterpret_cast<int4*>(ccN + 4 * ni) = c4;
+                            o++;
+                        }
+                    }
+                    continue;
+                }
                 const int x0 = bx[4 * nd], y0 = bx[4 * nd + 1], x1 = bx[4 * nd + 2], y1 = bx[4 * nd + 3];
                 const int mx = x0 + ((x1 - x0 + 1) >> 1), my = y0 + ((y1 - y0 + 1) >> 1);
                 for (int q = 0; q < 4; q++) {
@@ -1552,16 +1637,30 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
             for (int i = lane; i < T; i += 64) expand += szN[i] > 1 ? 1 : 0;
             expand = wave_sum(expand);
             const bool last = Lnew >= N || Lnew == prevSize || Lnew > NC - 4 || rounds >= 4096;
-            if (last)
+            if constexpr (kPyr) {
+                // (a fresh child's four counts were written with it; a survivor of a round that is not the last
+                // holds one key and its counts are never read)
+                const bool any = __ballot(deep) != 0ull;
+                if (lane == 0) s_round[4] = any ? 1 : 0;
+            } else if (last) {
                 for (int i = lane; i < Lnew; i += 64) ubest[i] = 0u;
-            else
+            } else {
                 for (int i = lane; i < 4 * Lnew; i += 64) ccN[i] = 0;
+            }
             if (lane == 0) { s_round[0] = T; s_round[1] = Lnew; s_round[2] = expand; s_round[3] = last ? 1 : 0; }
         }
         __syncthreads();
         DIST_PROF(20 + rounds);
         const int T = s_round[0], Lnew = s_round[1], nToExpand = s_round[2];
         const bool last = s_round[3] != 0;
+        if constexpr (kPyr) {
+            if (s_round[4] != 0) return true;
+            if (last)
+                for (int i = tid; i < Lnew; i += kDistThreads) {
+                    const int d = bxN[4 * i], ix = bxN[4 * i + 1], iy = bxN[4 * i + 2];
+                    ubest[i] = bestP[dist_pyr_off(d) + (iy << d) + ix];
+                }
+        }
         // four consecutive keys per thread per step (one state read and write, one 128-bit key read; their
         // dependent LDS chains -- state -> destination -> child box -- interleaved), the next step's keys
         // loaded before them, so the keys' L2 round trips (levels whose keys live in the HBM scratch) and
@@ -1594,7 +1693,9 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
                     if (g < n4) st.store4(g, ni, q);
             }
         };
-        if (last)
+        if constexpr (kPyr)
+            ;
+        else if (last)
             with_loc([&](auto loc) __attribute__((always_inline)) { key_pass(loc, DistLast{}); });
         else
             with_loc([&](auto loc) __attribute__((always_inline)) { key_pass(loc, DistMid{}); });
@@ -1618,6 +1719,91 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
             break;
         }
     }
+    return false;
+    };
+
+    // ---- which path: 0 = per-key state (several roots, or no room for the pyramids), 1 = pyramid path completed,
+    //      2 = pyramid path abandoned (then the per-key path from its gather on), 3 = pyramid path skipped up front.
+    //      A tree of n <= N keys cannot reach N nodes: it divides until every node holds one key, down to boxes a
+    //      few pixels wide (depth 7-9 at 640 x 480), so the pyramid path would only be abandoned: skipped.
+    int path = 0;
+    uint32_t* out = sel + (size_t)b * cfg.sel_per_frame + LV.sel_off;
+    if (nIni == 1 && rootX1 >= 0 && rootY1 >= 0 && dist_hist_bytes(rootX1, rootY1) <= dist_key_bytes(kc, kU8)) {
+        path = n > N ? 1 : 3;
+    }
+    if (path == 1) {
+        // path tables: the kDistD-bit path of every x and y in its 1-D interval tree (quad_of's midpoint rule and
+        // the child boxes' intervals [a, m] / [m, b]); the deepest bins zeroed
+        for (int i = tid; i <= rootX1 + rootY1 + 1; i += kDistThreads) {
+            const bool isx = i <= rootX1;
+            const int v = isx ? i : i - (rootX1 + 1);
+            int a = 0, e = isx ? rootX1 : rootY1, code = 0;
+#pragma unroll
+            for (int d = 0; d < kDistD; d++) {
+                const int m = a + ((e - a + 1) >> 1);
+                const bool hi = v >= m;
+                code = 2 * code + (hi ? 1 : 0);
+                a = hi ? m : a;
+                e = hi ? e : m;
+            }
+            xcode[i] = (uint8_t)code;   // (ycode follows xcode)
+        }
+        for (int i = tid; i < (1 << (2 * kDistD)); i += kDistThreads) {
+            cntP[dist_pyr_off(kDistD) + i] = 0;
+            bestP[dist_pyr_off(kDistD) + i] = 0u;
+        }
+        if (tid == 0) {
+            sizeB[0] = n;
+            cidB[0] = 0;
+            bxB[0] = bxB[1] = bxB[2] = bxB[3] = 0;   // (depth, ix, iy) of the root
+        }
+        __syncthreads();
+        gather(DistHist{});
+        __syncthreads();
+        DIST_PROF(1);
+        // both pyramids up to depth 0
+#pragma unroll
+        for (int d = kDistD - 1; d >= 0; d--) {
+            const int nn = 1 << (2 * d), rw = 2 << d;   // entries of depth d, row length of depth d + 1
+            for (int i = tid; i < 2 * nn; i += kDistThreads) {
+                const int e = i & (nn - 1), iy = e >> d, ix = e & ((1 << d) - 1);
+                const int c = dist_pyr_off(d + 1) + 2 * iy * rw + 2 * ix, o = dist_pyr_off(d) + e;
+                if (i < nn)
+                    cntP[o] = cntP[c] + cntP[c + 1] + cntP[c + rw] + cntP[c + rw + 1];
+                else
+                    bestP[o] = max(max(bestP[c], bestP[c + 1]), max(bestP[c + rw], bestP[c + rw + 1]));
+            }
+            __syncthreads();
+        }
+        if (tid < 4) childcnt[tid] = cntP[dist_pyr_off(1) + tid];   // quadrant q = (y half) << 1 | (x half)
+        __syncthreads();
+        L = 1;
+        DIST_PROF(2);
+        if (!run_rounds(DistPyr{})) {
+            DIST_PROF(40);
+            const uint32_t* slots = cell_slots + ((size_t)b * cfg.n_cells + LV.cell_begin) * cfg.cell_cap;
+            for (int i = tid; i < L; i += kDistThreads) {
+                const int slot = 0xFFFFFF - (int)(ubest[i] & 0xFFFFFFu);
+                out[i] = slots[min(slot, nCells * cfg.cell_cap - 1)];   // (the clamp keeps a broken list inside the level)
+            }
+            if (tid == 0) {
+                sel_count[b * cfg.nlevels + level] = L;
+                path_out[b * cfg.nlevels + level] = 1;
+            }
+#ifdef RGBD_PNP_PROFILE
+            if (threadIdx.x == 0 && b == 0 && level < 4) { g_dist_prof[level][42] = clock64(); g_dist_prof[level][43] = rounds; g_dist_prof[level][44] = n; g_dist_prof[level][45] = phase; g_dist_prof[level][47] = wall_clock64(); g_dist_prof[level][48] = 1; }
+#endif
+            return;
+        }
+        // abandoned: only LDS was written.  The cell counts and offsets again (the rounds reused them), then the
+        // per-key path from its start
+        path = 2;
+        load_cells();
+        reset_lists();
+    }
+    prepare_keys();
+    DIST_PROF(2);
+    run_rounds(DistKeys{});
     DIST_PROF(40);
     if (threadIdx.x == 0 && b == 0 && level < 4) { DIST_PROF(41); }
     // ---- retain the best key per node (:594-608): max response, first in key order
@@ -1632,7 +1818,6 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
         });
     }
     __syncthreads();
-    uint32_t* out = sel + (size_t)b * cfg.sel_per_frame + LV.sel_off;
     with_loc([&](auto loc) __attribute__((always_inline)) {
         const uint32_t* kbuf = decltype(loc)::keysL ? kk32 : keys;
         for (int i = tid; i < L; i += kDistThreads) {
@@ -1640,9 +1825,12 @@ __global__ __launch_bounds__(kDistThreads) __attribute__((amdgpu_waves_per_eu(RG
             out[i] = kbuf[min(k, n - 1)];   // (every node holds a key; the clamp keeps a broken list inside the level)
         }
     });
-    if (tid == 0) sel_count[b * cfg.nlevels + level] = L;
+    if (tid == 0) {
+        sel_count[b * cfg.nlevels + level] = L;
+        path_out[b * cfg.nlevels + level] = (uint8_t)path;
+    }
 #ifdef RGBD_PNP_PROFILE
-    if (threadIdx.x == 0 && b == 0 && level < 4) { g_dist_prof[level][42] = clock64(); g_dist_prof[level][43] = rounds; g_dist_prof[level][44] = n; g_dist_prof[level][45] = phase; g_dist_prof[level][47] = wall_clock64(); }
+    if (threadIdx.x == 0 && b == 0 && level < 4) { g_dist_prof[level][42] = clock64(); g_dist_prof[level][43] = rounds; g_dist_prof[level][44] = n; g_dist_prof[level][45] = phase; g_dist_prof[level][47] = wall_clock64(); g_dist_prof[level][48] = path; }
 #endif
 }
 
@@ -2322,17 +2510,17 @@ int distribute_key_capacity(long room, int NC)
 
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,
                        int scan_cap, int l0, int nlv, int kc, uint32_t* keys, uint16_t* node, int* sel_count,
-                       uint32_t* sel, int* err, int B, hipStream_t st)
+                       uint32_t* sel, int* err, uint8_t* path, int B, hipStream_t st)
 {
     const bool u8 = node_cap <= 256;
     const size_t lds = dist_node_bytes(node_cap, scan_cap) + dist_key_bytes(kc, u8);
     const int xcd = B % 8 == 0 ? 1 : 0;
     if (u8)
         return dispatch(k_distribute<uint8_t>, dim3(nlv * B), dim3(kDistThreads), lds, st, cell_count, cell_slots,
-                           d_cfg, keys, node, sel_count, sel, err, l0, nlv, kc, xcd);
+                           d_cfg, keys, node, sel_count, sel, err, path, l0, nlv, kc, xcd);
     else
         return dispatch(k_distribute<uint16_t>, dim3(nlv * B), dim3(kDistThreads), lds, st, cell_count, cell_slots,
-                           d_cfg, keys, node, sel_count, sel, err, l0, nlv, kc, xcd);
+                           d_cfg, keys, node, sel_count, sel, err, path, l0, nlv, kc, xcd);
 }
 
 #ifdef RGBD_PNP_PROFILE
@@ -2408,8 +2596,10 @@ void dist_prof_dump(hipStream_t st)
     for (int l = 0; l < 4; l++) {
         const long long* p = buf[l];
         const int rounds = (int)p[43];
-        fprintf(stderr, "[dist_prof] level %d n=%lld rounds=%d phase=%lld gather %lld roots %lld rounds:", l, p[44], rounds,
-                p[45], p[1] - p[0], p[2] - p[1]);
+        // path 1 (pyramids): gather = cell lists + histogram, roots = the reduction of both pyramids, and a round is
+        // its bookkeeping alone (the second figure: the last round's best-key reads)
+        fprintf(stderr, "[dist_prof] level %d path=%lld n=%lld rounds=%d phase=%lld gather %lld roots %lld rounds:", l, p[48], p[44],
+                rounds, p[45], p[1] - p[0], p[2] - p[1]);
         for (int r = 1; r <= rounds && r < 18; r++) fprintf(stderr, " %lld+%lld", p[20 + r] - p[1 + r], p[2 + r] - p[20 + r]);
         fprintf(stderr, " | best %lld total %lld wall %.1f us\n", p[42] - p[40], p[42] - p[0], (p[47] - p[46]) * 0.01);
     }

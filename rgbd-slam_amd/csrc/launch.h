@@ -14,10 +14,11 @@ hipError_t launch_pyr_tail(uint8_t* pyr, const ResizeY* rsy, const QuadX* qx, co
 hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* segs, int nseg, const ExtractCfg* d_cfg,
                  int* cell_count, uint32_t* cell_slots, int B, hipStream_t st, uint8_t* blur = nullptr,
                  int blur_threads = 0, const uint8_t* blur_tab = nullptr, int blur_waves = 0);
-// the quadtrees of levels [l0, l0 + nlv) of every frame; kc = LDS-resident keys per level
+// the quadtrees of levels [l0, l0 + nlv) of every frame; kc = LDS-resident keys per level; path: one byte per
+// (frame, level), the path the tree took (rgbd_debug_dist_path)
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,
                        int scan_cap, int l0, int nlv, int kc, uint32_t* keys, uint16_t* node, int* sel_count,
-                       uint32_t* sel, int* err, int B, hipStream_t st);
+                       uint32_t* sel, int* err, uint8_t* path, int B, hipStream_t st);
 size_t distribute_lds_bytes(int node_cap, int scan_cap);
 // keys per level (a multiple of 16) whose round state fits in room bytes of LDS beside the node arrays
 int distribute_key_capacity(long room, int node_cap);
