@@ -389,8 +389,10 @@ def sort_dmatch(dist, depth_limit=-1) -> np.ndarray:
     return order[:len(d)].copy()
 
 
-def ransac_se3(xyz1, xyz2, matches, prm: RansacParams, r: Rng, st: Sticky, flags2=None):
+def ransac_se3(xyz1, xyz2, matches, prm: RansacParams, r: Rng, st: Sticky, flags2=None, update_f2=None):
+    """update_f2 None: on exactly when flags2 is given."""
     m = len(matches)
+    update_f2 = (flags2 is not None) if update_f2 is None else update_f2
     T = np.zeros(16, np.float32)
     inl = np.zeros(max(m, 1), DMATCH_DTYPE)
     n_in = C.c_int32(0)
@@ -401,7 +403,7 @@ def ransac_se3(xyz1, xyz2, matches, prm: RansacParams, r: Rng, st: Sticky, flags
         fptr = flags2.ctypes.data
     ok = lib().orc_ransac_se3(np.ascontiguousarray(xyz1, np.float32), np.ascontiguousarray(xyz2, np.float32),
                               np.ascontiguousarray(matches) if m else np.zeros(1, DMATCH_DTYPE), m,
-                              C.byref(prm), C.byref(r), C.byref(st), int(flags2 is not None), fptr, T, inl,
+                              C.byref(prm), C.byref(r), C.byref(st), int(bool(update_f2)), fptr, T, inl,
                               C.byref(n_in), C.byref(rm))
     return bool(ok), T.reshape(4, 4), inl[:n_in.value].copy(), float(rm.value)
 

@@ -34,24 +34,44 @@ def _pkg_state(pkg, orng, ost):
     return r, s
 
 
-def _compare(pkg, oracle, ctx, xyz1, xyz2, matches, seed, sticky_cov=None, n2=None, prm_args=()):
+def _ransac_raw(pkg, ctx, xyz1, xyz2, matches, prm, r, st, update_f2, flags2, T, inl, n_in, rm, ok):
+    """rgbd_ransac_se3 itself (Context.ransac_se3 ties update_f2 to the presence of flags2 and raises on a refusal):
+    the status; the outputs are the caller's arrays."""
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    return pkg.lib().rgbd_ransac_se3(ctx._h, ptr(xyz1), len(xyz1), ptr(xyz2), len(xyz2), ptr(matches), len(matches),
+                                     C.byref(prm), C.byref(r), C.byref(st), int(update_f2), ptr(flags2), ptr(T), ptr(inl),
+                                     C.byref(n_in), C.byref(rm), C.byref(ok))
+
+
+def _compare(pkg, oracle, ctx, xyz1, xyz2, matches, seed, sticky_cov=None, n2=None, prm_args=(), update_f2=True,
+             flags2=True):
+    """update_f2 False: the flags are passed and must stay as they are; flags2 False: no flags at all."""
     orng = oracle.rng(seed)
     ost = oracle.Sticky()
     if sticky_cov is not None:
         ost.cov, ost.set = sticky_cov, 1
     prng, pst = _pkg_state(pkg, orng, ost)
     n2 = n2 or len(xyz2)
-    of = np.zeros(n2, np.uint8)
-    pf = np.zeros(n2, np.uint8)
-    ok_o, T_o, inl_o, rm_o = oracle.ransac_se3(xyz1, xyz2, matches, oracle.ransac_params(*prm_args), orng, ost, of)
-    ok_p, T_p, inl_p, rm_p = ctx.ransac_se3(xyz1, xyz2, matches, pkg.ransac_params(*prm_args), prng, pst, pf)
+    of = np.zeros(n2, np.uint8) if flags2 else None
+    pf = np.zeros(n2, np.uint8) if flags2 else None
+    ok_o, T_o, inl_o, rm_o = oracle.ransac_se3(xyz1, xyz2, matches, oracle.ransac_params(*prm_args), orng, ost, of,
+                                               update_f2=bool(update_f2 and flags2))
+    if update_f2 or not flags2:
+        ok_p, T_p, inl_p, rm_p = ctx.ransac_se3(xyz1, xyz2, matches, pkg.ransac_params(*prm_args), prng, pst, pf)
+    else:
+        x1, x2 = np.ascontiguousarray(xyz1, np.float32), np.ascontiguousarray(xyz2, np.float32)
+        mm = np.ascontiguousarray(matches, pkg.DMATCH_DTYPE)
+        T_p, inl_p = np.zeros(16, np.float32), np.zeros(max(len(mm), 1), pkg.DMATCH_DTYPE)
+        n_in, ok, rm = C.c_int32(0), C.c_int32(0), C.c_float(0)
+        assert _ransac_raw(pkg, ctx, x1, x2, mm, pkg.ransac_params(*prm_args), prng, pst, 0, pf, T_p, inl_p, n_in, rm, ok) == 0
+        ok_p, T_p, inl_p, rm_p = bool(ok.value), T_p.reshape(4, 4), inl_p[:n_in.value].copy(), float(rm.value)
     assert ok_o == ok_p
     assert np.array_equal(T_o.view(np.uint32), T_p.view(np.uint32)), (T_o, T_p)
     assert np.array_equal(inl_o, inl_p)
     assert np.float32(rm_o).view(np.uint32) == np.float32(rm_p).view(np.uint32), (rm_o, rm_p)
     assert list(orng.state) == list(prng.state) and (orng.f, orng.r) == (prng.f, prng.r), "RNG state diverged"
     assert ost.set == pst.set and ost.cov == pst.cov
-    assert np.array_equal(of, pf)
+    assert (of is None and pf is None) or np.array_equal(of, pf)
     return ok_o, T_o, len(inl_o)
 
 

@@ -4,8 +4,8 @@ into tests/ransac_loop_check.cpp and held to the oracle's own copies (orc_update
 the restated glibc rand()).
 
 RansacSE3::sampleMatches: neither tests/chain_model.py nor tests/lane_sort_model.py holds a sampler model and
-orc_solver exports none, so the check is against a restatement here with a set over the oracle's orc_random_int,
-together with the properties (ascending, distinct, n == SS, two draws per attempt)."""
+orc_solver exports none, so the check is against the restatement of tests/ransac_se3_cases.py with a set over the
+oracle's orc_random_int, together with the properties (ascending, distinct, n == SS, two draws per attempt)."""
 import ctypes as C
 import os
 import subprocess
@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from ransac_se3_cases import sample_model
 
 COUNTS = [5, 6, 61, 400, 4096]
 MAX_ITERS = [1, 2, 24, 500, 3000]
@@ -124,25 +125,6 @@ def replay_model(oracle, good, count, iterations):
             niters = f(0.85, (count - g) / count, 5, niters)
         it += 1
     return [it, niters, max_good, best]
-
-
-def sample_model(oracle, seed, M, SS, nh):
-    """RansacSE3::sampleMatches with a set, Random::randomInt from the oracle: (ids, rand() calls so far) per hypothesis"""
-    L = oracle.lib()
-    L.orc_random_int.restype = C.c_int
-    L.orc_random_int.argtypes = [C.POINTER(oracle.Rng), C.c_int, C.c_int]
-    rng, calls, out = oracle.rng(seed), 0, []
-    for _ in range(nh):
-        ids, safety = set(), 0
-        while len(ids) < SS and M >= SS:
-            a, b = L.orc_random_int(C.byref(rng), 0, M - 1), L.orc_random_int(C.byref(rng), 0, M - 1)
-            calls += 2
-            ids.add(min(a, b))
-            safety += 1
-            if safety > 10000:
-                break
-        out.append((sorted(ids), calls))
-    return out
 
 
 SAMPLE_CASES = [(4, 4, 200), (10, 4, 200), (100, 4, 200), (2304, 4, 200), (8, 8, 100), (3, 4, 5)]
