@@ -9,6 +9,8 @@
 //   rgbd::RansacSE3      <- RansacSE3::compute + rmse / mvInliers / mT21   Solver/SolverSE3.h:15-57
 //   rgbd::Gicp           <- Gicp::compute / align + setters                 Solver/Gicp.h:10-57
 //   rgbd::PnPRansac      <- PnPRansac::compute                             Solver/PnPRansac.h
+//   rgbd::Vocabulary     <- DBoW3::Vocabulary (transform, score, size; TF_IDF + L1_NORM)  Core/Frame.cpp:243-249
+//   rgbd::LoopDetector   <- LoopDetector::add / obtainCandidates            PlaceRecognition/LoopDetector.cpp:22-84
 //
 // No OpenCV/Eigen types: poses are row-major float[16] (cv::Mat 4x4 CV_32F layout), keypoints and
 // matches are the byte-identical rgbd_keypoint / rgbd_dmatch.  INTEGRATION.md shows the thin
@@ -18,8 +20,13 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -159,6 +166,111 @@ private:
     float scale_ = 1.2f;
 };
 
+using BowVector = std::map<uint32_t, double>;                       // DBoW3::BowVector: word id -> value
+using FeatureVector = std::map<uint32_t, std::vector<unsigned>>;    // DBoW3::FeatureVector: node id -> feature indices
+
+// DBoW3::Vocabulary over the device operator (DESIGN.md "Bag-of-words and loop detection definition").  The tree is
+// uploaded to the context once; transform and score run on the device.
+class Vocabulary {
+public:
+    // node arrays as rgbd_voc_set takes them (node 0 the root)
+    Vocabulary(rgbd_ctx* ctx, int k, int L, const std::vector<int32_t>& parent, const std::vector<uint8_t>& descriptor,
+               const std::vector<double>& weight, const std::vector<uint8_t>& is_leaf, const std::vector<int32_t>& word_id,
+               int weighting = RGBD_VOC_TF_IDF, int scoring = RGBD_VOC_L1_NORM)
+        : ctx_(ctx)
+    {
+        words_ = 0;
+        for (uint8_t l : is_leaf) words_ += l ? 1u : 0u;
+        check(ctx, rgbd_voc_set(ctx, k, L, weighting, scoring, 32, (int64_t)parent.size(), parent.data(), descriptor.data(),
+                                weight.data(), is_leaf.data(), word_id.data()), "Vocabulary");
+    }
+    // DBoW3's text YAML, uncompressed (the layout recalled in rgbd-slam_amd/vocabulary.py, unpinned)
+    static std::shared_ptr<Vocabulary> load(rgbd_ctx* ctx, const std::string& path)
+    {
+        FILE* f = std::fopen(path.c_str(), "rb");
+        if (!f) throw Error("Vocabulary: cannot open " + path);
+        std::string text;
+        char buf[65536];
+        for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+        std::fclose(f);
+        auto num = [&](const char* key, size_t from) -> double {
+            const size_t at = text.find(key, from);
+            if (at == std::string::npos) throw Error(std::string("Vocabulary: no ") + key);
+            return std::strtod(text.c_str() + at + std::strlen(key), nullptr);
+        };
+        const int k = (int)num(" k:", 0), L = (int)num(" L:", 0);
+        const int scoring = (int)num("scoringType:", 0), weighting = (int)num("weightingType:", 0);
+        const size_t words_at = text.find("words:");
+        if (words_at == std::string::npos) throw Error("Vocabulary: no words list");
+        std::vector<int32_t> parent(1, 0), word(1, -1);
+        std::vector<uint8_t> desc(32, 0), leaf(1, 0);
+        std::vector<double> weight(1, 0.0);
+        for (size_t at = text.find("nodeId:"); at != std::string::npos && at < words_at; at = text.find("nodeId:", at + 1)) {
+            const size_t id = (size_t)num("nodeId:", at);
+            if (id >= parent.size()) {
+                parent.resize(id + 1, 0); word.resize(id + 1, -1); leaf.resize(id + 1, 0); weight.resize(id + 1, 0.0);
+                desc.resize((id + 1) * 32, 0);
+            }
+            parent[id] = (int32_t)num("parentId:", at);
+            weight[id] = num("weight:", at);
+            const size_t d = text.find("dbw3", at);
+            if (d == std::string::npos) throw Error("Vocabulary: a node without a descriptor");
+            char* q = nullptr;
+            const long type = std::strtol(text.c_str() + d + 4, &q, 10), cols = std::strtol(q, &q, 10);
+            if (type != 0 || cols != 32) throw Error("Vocabulary: not a 32-byte CV_8U descriptor");
+            for (int b = 0; b < 32; b++) desc[id * 32 + b] = (uint8_t)std::strtol(q, &q, 10);
+        }
+        for (size_t at = text.find("wordId:", words_at); at != std::string::npos; at = text.find("wordId:", at + 1)) {
+            const size_t node = (size_t)num("nodeId:", at);
+            if (node >= parent.size()) throw Error("Vocabulary: a word on an unknown node");
+            leaf[node] = 1;
+            word[node] = (int32_t)num("wordId:", at);
+        }
+        return std::make_shared<Vocabulary>(ctx, k, L, parent, desc, weight, leaf, word, weighting, scoring);
+    }
+    unsigned size() const { return words_; }
+    rgbd_ctx* ctx() const { return ctx_; }
+    // transform(features, BowVector, FeatureVector, levelsup) of n descriptors (n x 32 bytes)
+    void transform(const uint8_t* desc, int n, BowVector& v, FeatureVector& fv, int levelsup) const
+    {
+        const size_t m = (size_t)std::max(n, 1);
+        std::vector<uint32_t> ids(m);
+        std::vector<double> vals(m);
+        std::vector<int32_t> node(m), idx(m);
+        int32_t nw = 0, nf = 0;
+        check(ctx_, rgbd_bow_transform(ctx_, desc, n, levelsup, ids.data(), vals.data(), &nw, node.data(), idx.data(), &nf),
+              "Vocabulary::transform");
+        v.clear();
+        fv.clear();
+        for (int i = 0; i < nw; i++) v.emplace_hint(v.end(), ids[i], vals[i]);
+        for (int i = 0; i < nf; i++) fv[(uint32_t)node[i]].push_back((unsigned)idx[i]);
+    }
+    double score(const BowVector& a, const BowVector& b) const
+    {
+        std::vector<uint32_t> ia, ib;
+        std::vector<double> va, vb;
+        flatten(a, ia, va);
+        flatten(b, ib, vb);
+        double s = 0.0;
+        check(ctx_, rgbd_bow_score(ctx_, ia.data(), va.data(), (int32_t)ia.size(), ib.data(), vb.data(), (int32_t)ib.size(), &s),
+              "Vocabulary::score");
+        return s;
+    }
+    static void flatten(const BowVector& v, std::vector<uint32_t>& ids, std::vector<double>& vals)
+    {
+        ids.clear();
+        vals.clear();
+        for (const auto& kv : v) {
+            ids.push_back(kv.first);
+            vals.push_back(kv.second);
+        }
+    }
+
+private:
+    rgbd_ctx* ctx_;
+    unsigned words_ = 0;
+};
+
 class Frame {
 public:
     using Ptr = std::shared_ptr<Frame>;
@@ -166,6 +278,7 @@ public:
     Frame(const uint8_t* bgr, const uint16_t* depth, double timeStamp, const ExtractorBase& ex)
         : mTimeStamp(timeStamp), mCamera(ex.camera())
     {
+        mnId = nextId()++;                                           // Core/Frame.cpp: mnId = nNextId++
         rgbd_ctx* c = ex.ctx();
         const int cap = rgbd_max_keypoints(c);
         mvKeys.resize(cap);
@@ -236,6 +349,16 @@ public:
         for (int i = 0; i < N; i++) z[i] = mvKeys3Dc[3 * (size_t)i + 2];
         return z;
     }
+    // Frame::computeBoW (Core/Frame.cpp:243-249): once per frame, levelsup 4
+    void computeBoW(const Vocabulary& voc)
+    {
+        if (mBowVec.empty()) voc.transform(mDescriptors.data(), N, mBowVec, mFeatVec, 4);
+    }
+    int id() const { return mnId; }
+    static int& nextId() { static int next = 0; return next; }      // Frame::nNextId
+    // connections are kept as plain pointers: the map that owns the keyframes outlives them
+    void addConnection(Frame* kf) { mspConnectedKFs.insert(kf); }
+    const std::set<Frame*>& getConnectedKFs() const { return mspConnectedKFs; }
 
     static constexpr int FRAME_GRID_COLS = 64, FRAME_GRID_ROWS = 48;   // Core/Frame.h
     int N = 0;
@@ -249,6 +372,74 @@ public:
     std::vector<float> mvKeys3Dc;           // N x 3
     std::vector<uint8_t> mvbOutlier;
     Pose mTcw = identity();
+    int mnId = 0;
+    BowVector mBowVec;
+    FeatureVector mFeatVec;
+    double mScore = 0.0;
+    std::set<Frame*> mspConnectedKFs;
+};
+
+// LoopDetector over the context's keyframe database: add uploads the keyframe's BoW vector; obtainCandidates scores
+// the query against every entry on the device (two launches, one per argument order) and applies the reference's
+// candidate rules on the host (rgbd_loop_candidates).
+class LoopDetector {
+public:
+    explicit LoopDetector(std::shared_ptr<Vocabulary> voc, int interval = 10) : voc_(std::move(voc)), mnInterval(interval)
+    {
+        check(voc_->ctx(), rgbd_loopdb_clear(voc_->ctx()), "LoopDetector");
+    }
+    void add(const Frame::Ptr& pKF)
+    {
+        std::vector<uint32_t> ids;
+        std::vector<double> vals;
+        Vocabulary::flatten(pKF->mBowVec, ids, vals);
+        int32_t e = 0;
+        check(voc_->ctx(), rgbd_loopdb_add(voc_->ctx(), ids.data(), vals.data(), (int32_t)ids.size(), &e), "LoopDetector::add");
+        entries_.push_back(pKF);
+    }
+    std::vector<Frame::Ptr> obtainCandidates(const Frame::Ptr& pKF)
+    {
+        std::vector<Frame::Ptr> out;
+        const std::set<Frame*>& conn = pKF->getConnectedKFs();
+        if (conn.empty()) return out;
+        rgbd_ctx* c = voc_->ctx();
+        const int32_t E = (int32_t)entries_.size();
+        std::vector<uint32_t> ids;
+        std::vector<double> vals;
+        Vocabulary::flatten(pKF->mBowVec, ids, vals);
+        std::vector<double> rev((size_t)std::max(E, 1)), score(rev.size());
+        std::vector<int32_t> shared(rev.size()), first(rev.size()), fid(rev.size());
+        std::vector<uint8_t> skip(rev.size(), 0);
+        int32_t n = 0;
+        check(c, rgbd_loopdb_query(c, ids.data(), vals.data(), (int32_t)ids.size(), 0, E, rev.data(), shared.data(), first.data(), &n),
+              "LoopDetector::obtainCandidates");
+        check(c, rgbd_loopdb_query(c, ids.data(), vals.data(), (int32_t)ids.size(), 1, E, score.data(), shared.data(), first.data(), &n),
+              "LoopDetector::obtainCandidates");
+        double minScore = std::numeric_limits<double>::max();
+        for (int32_t e = 0; e < E; e++) {
+            Frame* k = entries_[e].get();
+            fid[e] = k->id();
+            if (k == pKF.get()) skip[e] = 1;
+            if (k == pKF.get() || !conn.count(k)) continue;
+            skip[e] = 1;
+            if (rev[e] < minScore) minScore = rev[e];
+        }
+        int32_t pick[5], np = 0;
+        if (rgbd_loop_candidates(E, score.data(), shared.data(), first.data(), fid.data(), skip.data(), pKF->id(), minScore, mnInterval,
+                                 pick, &np) != RGBD_OK)
+            throw Error("LoopDetector::obtainCandidates: bad arguments");
+        for (int32_t i = 0; i < np; i++) {
+            entries_[pick[i]]->mScore = score[pick[i]];
+            out.push_back(entries_[pick[i]]);
+        }
+        return out;
+    }
+    void setInterval(int interval) { mnInterval = interval; }
+
+private:
+    std::shared_ptr<Vocabulary> voc_;
+    int mnInterval;
+    std::vector<Frame::Ptr> entries_;
 };
 
 class Matcher {

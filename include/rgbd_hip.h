@@ -557,6 +557,66 @@ rgbd_status rgbd_pg_chi2(const rgbd_posegraph* g, double* chi2);
 rgbd_status rgbd_pg_optimize(rgbd_posegraph* g, int32_t iterations, double* chi2, int32_t* iterations_done);
 rgbd_status rgbd_pg_vertex(const rgbd_posegraph* g, int32_t id, double* Twc);
 
+/* ------------------------------------------------------------------ bag of words and the loop database */
+/* DBoW3's vocabulary tree, transform and L1 score as the reference drives them (Frame::computeBoW, Core/Frame.cpp:243-249;
+ * LoopDetector, PlaceRecognition/LoopDetector.cpp:22-84).  DBoW3 is absent: the operator is the definition in DESIGN.md
+ * "Bag-of-words and loop detection definition", written from the reference's callers and recalled DBoW3 semantics;
+ * parity with the library is unpinned.
+ *
+ * rgbd_voc_set uploads a tree of n_nodes nodes, node 0 the root: parent[i] (parent[0] ignored), descriptor[i] (32
+ * bytes), weight[i], is_leaf[i], word_id[i] (read on leaves: 0 .. words - 1, once each).  The children of a node are
+ * ordered by node id.  The vocabulary belongs to the context and is immutable until the next rgbd_voc_set /
+ * rgbd_voc_clear.  RGBD_ERR_UNSUPPORTED before any copy: weighting / scoring other than TF_IDF / L1_NORM, desc_bytes
+ * != 32, k outside [2, 32], L outside [1, 10], n_nodes >= 2^31, an inner node with 0 or more than k children (a leaf
+ * root included), a node below level L, a weight that is not finite and >= 0.  A malformed tree: RGBD_ERR_ARG. */
+enum { RGBD_VOC_TF_IDF = 0, RGBD_VOC_TF = 1, RGBD_VOC_IDF = 2, RGBD_VOC_BINARY = 3 };               /* DBoW3::WeightingType */
+enum { RGBD_VOC_L1_NORM = 0, RGBD_VOC_L2_NORM = 1, RGBD_VOC_CHI_SQUARE = 2, RGBD_VOC_KL = 3,
+       RGBD_VOC_BHATTACHARYYA = 4, RGBD_VOC_DOT_PRODUCT = 5 };                                      /* DBoW3::ScoringType */
+rgbd_status rgbd_voc_set(rgbd_ctx* ctx, int32_t k, int32_t L, int32_t weighting, int32_t scoring, int32_t desc_bytes,
+                         int64_t n_nodes, const int32_t* parent, const uint8_t* descriptor, const double* weight,
+                         const uint8_t* is_leaf, const int32_t* word_id);
+rgbd_status rgbd_voc_clear(rgbd_ctx* ctx);
+/* Vocabulary::transform(features, BowVector, FeatureVector, levelsup) of n host descriptors (n x 32 bytes): the BoW
+ * vector (bow_ids ascending, bow_vals, *n_words entries) and the feature vector as (fv_node, fv_idx) pairs ascending
+ * (*n_fv entries); every output array holds n slots.  n > 4096: RGBD_ERR_UNSUPPORTED before any copy or launch; no
+ * vocabulary or levelsup < 0: RGBD_ERR_ARG.  One k_bow_words and one k_bow_vector launch. */
+rgbd_status rgbd_bow_transform(rgbd_ctx* ctx, const uint8_t* desc, int32_t n, int32_t levelsup, uint32_t* bow_ids,
+                               double* bow_vals, int32_t* n_words, int32_t* fv_node, int32_t* fv_idx, int32_t* n_fv);
+/* P frames in the same two launches: desc = the frames' descriptors one after the other (counts[p] rows each); frame
+ * p's outputs start at its first descriptor's row, n_words[p] / n_fv[p] of them written. */
+rgbd_status rgbd_bow_transform_batch(rgbd_ctx* ctx, int32_t P, const uint8_t* desc, const int32_t* counts, int32_t levelsup,
+                                     uint32_t* bow_ids, double* bow_vals, int32_t* n_words, int32_t* fv_node,
+                                     int32_t* fv_idx, int32_t* n_fv);
+/* The same from the device descriptors of the last extraction (frame[p] in [0, B)): no descriptor crosses the host.
+ * Frame p's outputs are the rgbd_max_keypoints slots from p * rgbd_max_keypoints. */
+rgbd_status rgbd_bow_transform_frames(rgbd_ctx* ctx, int32_t P, const int32_t* frame, int32_t levelsup, uint32_t* bow_ids,
+                                      double* bow_vals, int32_t* n_words, int32_t* fv_node, int32_t* fv_idx, int32_t* n_fv);
+/* The descent alone: per descriptor the word id, its weight, the node id at level L - levelsup (0 when that level
+ * is <= 0 or below the leaf) and the children taken (path: n x 10 bytes, 255 below the leaf). */
+rgbd_status rgbd_debug_bow_words(rgbd_ctx* ctx, const uint8_t* desc, int32_t n, int32_t levelsup, int32_t* word,
+                                 double* weight, int32_t* node, uint8_t* path);
+/* L1Scoring::score(a, b) on the device; the argument order matters to the last bit.  Ids strictly ascending, at
+ * most 4096 per vector. */
+rgbd_status rgbd_bow_score(rgbd_ctx* ctx, const uint32_t* ids_a, const double* val_a, int32_t na, const uint32_t* ids_b,
+                           const double* val_b, int32_t nb, double* score);
+/* The keyframe database (LoopDetector::add's inverted file as the vectors themselves, device resident): add appends
+ * one BoW vector, *entry = its index.  query scores one vector against every entry in one k_bow_score launch:
+ * query_first != 0 is score(query, entry) (LoopDetector.cpp:70), 0 is score(entry, query) (:43); per entry the
+ * score, the number of shared words and the smallest shared word id (-1: none).  *n_entries = the entry count; cap
+ * below it: RGBD_ERR_CAPACITY.  An empty database launches nothing. */
+rgbd_status rgbd_loopdb_add(rgbd_ctx* ctx, const uint32_t* ids, const double* vals, int32_t n, int32_t* entry);
+rgbd_status rgbd_loopdb_query(rgbd_ctx* ctx, const uint32_t* ids, const double* vals, int32_t n, int32_t query_first,
+                              int32_t cap, double* score, int32_t* n_shared, int32_t* min_shared, int32_t* n_entries);
+rgbd_status rgbd_loopdb_clear(rgbd_ctx* ctx);
+int32_t rgbd_loopdb_size(const rgbd_ctx* ctx);
+/* LoopDetector::obtainCandidates' host rules (:48-83) over a query's arrays: the entries that share a word and are
+ * not skipped (skip[e] != 0: the query itself and its connected keyframes), in the inverted file's order (smallest
+ * shared word, then insertion), kept when score > min_score and abs(frame_id[e] - query_id) > interval; more than
+ * five kept: std::sort by score descending and the first five.  out holds min(n, 5) entry indices. */
+rgbd_status rgbd_loop_candidates(int32_t n, const double* score, const int32_t* n_shared, const int32_t* min_shared,
+                                 const int32_t* frame_id, const uint8_t* skip, int32_t query_id, double min_score,
+                                 int32_t interval, int32_t* out, int32_t* n_out);
+
 /* ------------------------------------------------------------------ measurement */
 /* Per-kernel HIP-event timing on the context stream (off by default). */
 rgbd_status rgbd_set_timing(rgbd_ctx* ctx, int32_t enable);

@@ -9,6 +9,8 @@ that mirror the reference's operator surfaces for this path:
   Context.projection_match(...)    <- Matcher::projectionMatch     Features/Matcher.cpp:35-104
   Context.pnp_solver(...)          <- PnPSolver::compute           Solver/PnPSolver.cpp:31-150
   Context.ransac_umeyama(...)      <- Ransac::compute              Solver/Ransac.cpp:46-181
+  Context.bow_transform(desc)      <- Frame::computeBoW            Core/Frame.cpp:243-249
+  Context.loopdb_add / loopdb_query, loop_candidates <- LoopDetector  PlaceRecognition/LoopDetector.cpp:22-84
   RansacSE3(...).compute(F1, F2, m) <- RansacSE3::compute          Solver/SolverSE3.cpp:23-133
 
 The GPU library is mandatory: there is no CPU fallback.  Importing works without a GPU
@@ -208,6 +210,18 @@ _SIGS = {
     "rgbd_debug_ransac_umeyama": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, C.POINTER(UmeyamaParams), C.POINTER(Rng), _vp,
                                          _vp, _vp, _PI, _PI, _PI, _i32, _vp, _vp, _vp, _PI, _i32, _vp, _PI]),
     "rgbd_ransac_umeyama_pose": (None, [_vp, _vp, _vp]),
+    "rgbd_voc_set": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "rgbd_voc_clear": (_i32, [_vp]),
+    "rgbd_bow_transform": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _PI, _vp, _vp, _PI]),
+    "rgbd_bow_transform_batch": (_i32, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbd_bow_transform_frames": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rgbd_debug_bow_words": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "rgbd_bow_score": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, C.POINTER(C.c_double)]),
+    "rgbd_loopdb_add": (_i32, [_vp, _vp, _vp, _i32, _PI]),
+    "rgbd_loopdb_query": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _PI]),
+    "rgbd_loopdb_clear": (_i32, [_vp]),
+    "rgbd_loopdb_size": (_i32, [_vp]),
+    "rgbd_loop_candidates": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _i32, _vp, _PI]),
     "rgbd_gicp": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI, _PI]),
     "rgbd_gicp_compute": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(GicpParams), _vp, _PI]),
     "rgbd_set_tracking_gicp": (_i32, [_vp, C.POINTER(GicpParams)]),
@@ -319,6 +333,22 @@ def rng(seed: int) -> Rng:
     r = Rng()
     lib().rgbd_rng_seed(C.byref(r), seed)
     return r
+
+
+def loop_candidates(score, n_shared, min_shared, frame_id, skip, query_id: int, min_score: float, interval: int = 10):
+    """rgbd_loop_candidates: the entry indices LoopDetector::obtainCandidates returns, in its order (host only)."""
+    score = np.ascontiguousarray(score, np.float64)
+    ns, mw = np.ascontiguousarray(n_shared, np.int32), np.ascontiguousarray(min_shared, np.int32)
+    fid, sk = np.ascontiguousarray(frame_id, np.int32), np.ascontiguousarray(skip, np.uint8)
+    n = len(score)
+    if not (len(ns) == len(mw) == len(fid) == len(sk) == n):
+        raise ValueError("loop_candidates: array lengths differ")
+    out, k = np.zeros(5, np.int32), C.c_int32(0)
+    st = lib().rgbd_loop_candidates(n, _ptr(score), _ptr(ns), _ptr(mw), _ptr(fid), _ptr(sk), int(query_id), float(min_score),
+                                    int(interval), _ptr(out), C.byref(k))
+    if st != 0:
+        raise RgbdError(f"loop_candidates: status {st}")
+    return out[:k.value].copy()
 
 
 class Context:
@@ -896,6 +926,106 @@ class Context:
         out = np.zeros(16, np.float32)
         lib().rgbd_ransac_umeyama_pose(_ptr(a), _ptr(b), _ptr(out))
         return out.reshape(4, 4)
+
+    # --- bag of words and the loop database (DESIGN.md "Bag-of-words and loop detection definition")
+    def voc_set(self, voc):
+        """rgbd_voc_set from a vocabulary.Vocabulary (or any object with its array fields)."""
+        parent = np.ascontiguousarray(voc.parent, np.int32)
+        desc = np.ascontiguousarray(voc.descriptor, np.uint8)
+        weight = np.ascontiguousarray(voc.weight, np.float64)
+        leaf = np.ascontiguousarray(voc.is_leaf, np.uint8)
+        word = np.ascontiguousarray(voc.word_id, np.int32)
+        n = len(parent)
+        if not (len(desc) == len(weight) == len(leaf) == len(word) == n) or desc.ndim != 2:
+            raise ValueError("voc_set: the node arrays differ in length")
+        self._check(lib().rgbd_voc_set(self._h, int(voc.k), int(voc.L), int(voc.weighting), int(voc.scoring), desc.shape[1], n,
+                                       _ptr(parent), _ptr(desc), _ptr(weight), _ptr(leaf), _ptr(word)), "voc_set")
+
+    def voc_clear(self):
+        self._check(lib().rgbd_voc_clear(self._h), "voc_clear")
+
+    @staticmethod
+    def _bow_result(ids, vals, nw, fvn, fvi, nfv):
+        return dict(ids=ids[:nw].copy(), vals=vals[:nw].copy(), fv_node=fvn[:nfv].copy(), fv_idx=fvi[:nfv].copy())
+
+    def bow_transform(self, desc, levelsup: int = 4):
+        """rgbd_bow_transform: dict(ids u32 ascending, vals f64, fv_node, fv_idx) of one frame's descriptors."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, m = len(desc), max(len(desc), 1)
+        ids, vals = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        fvn, fvi = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        nw, nfv = C.c_int32(0), C.c_int32(0)
+        self._check(lib().rgbd_bow_transform(self._h, _ptr(desc), n, levelsup, _ptr(ids), _ptr(vals), C.byref(nw), _ptr(fvn),
+                                             _ptr(fvi), C.byref(nfv)), "bow_transform")
+        return self._bow_result(ids, vals, nw.value, fvn, fvi, nfv.value)
+
+    def bow_transform_batch(self, descs, levelsup: int = 4):
+        """rgbd_bow_transform_batch over a list of descriptor arrays: a list of bow_transform's dicts."""
+        descs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descs]
+        P = len(descs)
+        counts = np.array([len(d) for d in descs] + [0], np.int32)
+        D = np.ascontiguousarray(np.concatenate(descs + [np.zeros((1, 32), np.uint8)]))
+        m = len(D)
+        ids, vals = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        fvn, fvi = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        nw, nfv = np.zeros(P + 1, np.int32), np.zeros(P + 1, np.int32)
+        self._check(lib().rgbd_bow_transform_batch(self._h, P, _ptr(D), _ptr(counts), levelsup, _ptr(ids), _ptr(vals), _ptr(nw),
+                                                   _ptr(fvn), _ptr(fvi), _ptr(nfv)), "bow_transform_batch")
+        out, o = [], 0
+        for p in range(P):
+            out.append(self._bow_result(ids[o:], vals[o:], nw[p], fvn[o:], fvi[o:], nfv[p]))
+            o += int(counts[p])
+        return out
+
+    def bow_transform_frames(self, frames, levelsup: int = 4):
+        """rgbd_bow_transform_frames over frames of the last extract_batch: a list of bow_transform's dicts."""
+        fr = np.ascontiguousarray(frames, np.int32)
+        P, K = len(fr), self.kp_cap
+        m = max(P, 1) * K
+        ids, vals = np.zeros(m, np.uint32), np.zeros(m, np.float64)
+        fvn, fvi = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        nw, nfv = np.zeros(max(P, 1), np.int32), np.zeros(max(P, 1), np.int32)
+        self._check(lib().rgbd_bow_transform_frames(self._h, P, _ptr(fr), levelsup, _ptr(ids), _ptr(vals), _ptr(nw), _ptr(fvn),
+                                                    _ptr(fvi), _ptr(nfv)), "bow_transform_frames")
+        return [self._bow_result(ids[p * K:], vals[p * K:], nw[p], fvn[p * K:], fvi[p * K:], nfv[p]) for p in range(P)]
+
+    def debug_bow_words(self, desc, levelsup: int = 4):
+        """rgbd_debug_bow_words: dict(word, weight, node, path (n, 10) u8 with 255 below the leaf)."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, m = len(desc), max(len(desc), 1)
+        word, node = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        weight, path = np.zeros(m, np.float64), np.zeros((m, 10), np.uint8)
+        self._check(lib().rgbd_debug_bow_words(self._h, _ptr(desc), n, levelsup, _ptr(word), _ptr(weight), _ptr(node),
+                                               _ptr(path)), "debug_bow_words")
+        return dict(word=word[:n], weight=weight[:n], node=node[:n], path=path[:n])
+
+    def bow_score(self, a, b) -> float:
+        """rgbd_bow_score: L1Scoring::score(a, b) of two (ids, vals) vectors."""
+        ia, va = np.ascontiguousarray(a[0], np.uint32), np.ascontiguousarray(a[1], np.float64)
+        ib, vb = np.ascontiguousarray(b[0], np.uint32), np.ascontiguousarray(b[1], np.float64)
+        s = C.c_double(0)
+        self._check(lib().rgbd_bow_score(self._h, _ptr(ia), _ptr(va), len(ia), _ptr(ib), _ptr(vb), len(ib), C.byref(s)),
+                    "bow_score")
+        return s.value
+
+    def loopdb_add(self, ids, vals) -> int:
+        ids, vals = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(vals, np.float64)
+        e = C.c_int32(0)
+        self._check(lib().rgbd_loopdb_add(self._h, _ptr(ids), _ptr(vals), len(ids), C.byref(e)), "loopdb_add")
+        return e.value
+
+    def loopdb_query(self, ids, vals, query_first: bool = True):
+        """rgbd_loopdb_query: (score f64, n_shared, min_shared) per database entry."""
+        ids, vals = np.ascontiguousarray(ids, np.uint32), np.ascontiguousarray(vals, np.float64)
+        cap = max(lib().rgbd_loopdb_size(self._h), 1)
+        score, ns, mw = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int32(0)
+        self._check(lib().rgbd_loopdb_query(self._h, _ptr(ids), _ptr(vals), len(ids), int(query_first), cap, _ptr(score),
+                                            _ptr(ns), _ptr(mw), C.byref(n)), "loopdb_query")
+        return score[:n.value], ns[:n.value], mw[:n.value]
+
+    def loopdb_clear(self):
+        self._check(lib().rgbd_loopdb_clear(self._h), "loopdb_clear")
 
     def pnp_ransac_batch(self, problems, K4, prm: PnpParams | None = None):
         """solvePnPRansac on each (p3 [n,3], p2 [n,2]) of `problems`; one pass for all of them.

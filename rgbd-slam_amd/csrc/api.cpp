@@ -726,6 +726,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::proj_free(c);
     rgbd::pnpba_free(c);
     rgbd::umeyama_free(c);
+    rgbd::bow_free(c);
     rgbd::svo_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);

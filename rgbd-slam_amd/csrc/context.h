@@ -11,7 +11,7 @@
 #include "rgbd_internal.h"
 
 namespace rgbd {
-struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS;
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS;
 // the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
 struct OutSet {
     int* count = nullptr;
@@ -93,6 +93,7 @@ struct rgbd_ctx {
     rgbd::ProjWS* proj = nullptr;        // projection-guided matching (project_host.cpp)
     rgbd::BaWS* pnpba = nullptr;         // motion-only bundle adjustment, PnPSolver (pnpba_host.cpp)
     rgbd::UmWS* umeyama = nullptr;       // Umeyama RANSAC, Ransac (umeyama_host.cpp)
+    rgbd::BowWS* bow = nullptr;          // vocabulary, BoW transform and loop database (bow_host.cpp)
     bool bounds_set = false;             // rgbd_image_bounds: computed on first use
     rgbd_bounds bounds{};
     rgbd_gicp_params track_gicp{10, 20, 0.07, 1e-9, 2e-3, 1e-3, 4, 1};
@@ -144,6 +145,7 @@ void cloud_free(rgbd_ctx* c);    // cloud_host.cpp
 void proj_free(rgbd_ctx* c);     // project_host.cpp
 void pnpba_free(rgbd_ctx* c);    // pnpba_host.cpp
 void umeyama_free(rgbd_ctx* c);  // umeyama_host.cpp
+void bow_free(rgbd_ctx* c);      // bow_host.cpp
 // svo_host.cpp: the Extractor(SVO, BRIEF, NORMAL) front end of an rgbd_create_svo context
 rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p);   // before the output allocations
 rgbd_status svo_alloc(rgbd_ctx* c);

@@ -2,13 +2,20 @@
 reference's keyframe policy (Tracking::needKeyFrame, System/Tracking.cpp:201-225) and the local-edge
 search that reuses the device Matcher + RansacSE3 (PoseGraph::createLocalEdges, :128-182):
 
-  insert_keyframe  <- PoseGraph::updateGraph (:105-126) without loop detection: node, edge with the
+  insert_keyframe  <- PoseGraph::insertKeyFrame + updateGraph (:105-126, :289-296): node, edge with the
                       reference keyframe (setMeasurementFromState), local edges to the keyframes whose
                       camera centres lie within 0.5 m (Matcher(0.9) >= 30 matches, RansacSE3(200, 30,
-                      3.0f, 4).compute(pKFi, cur, matches, updateF2=false), measurement mT21)
+                      3.0f, 4).compute(pKFi, cur, matches, updateF2=false), measurement mT21); with a
+                      vocabulary also Frame::computeBoW, LoopDetector::add and detect_loop, and after a
+                      detected loop PoseGraph::run's optimize(20) (:69-72)
+  detect_loop      <- PoseGraph::detectLoop (:245-287) over LoopDetector::obtainCandidates
+                      (PlaceRecognition/LoopDetector.cpp:28-84): the BoW transform, the database scores and
+                      the match + RansacSE3 run on the device, the candidate rules on the host
   optimize         <- PoseGraph::optimize (:368-386): vertex 0 fixed, LM, corrected poses
-Loop closure needs the DBoW3 vocabulary (PlaceRecognition/LoopDetector), which is absent: out of
-scope.  Keyframe features are those of the keyframe's own extraction, with the
+Loop detection needs a DBoW3 vocabulary, which the user supplies (vocabulary.py; DESIGN.md "Bag-of-words
+and loop detection definition"); without one the class builds the graph it built before loop detection
+existed.  Tracking::correct after a loop (System/Tracking.cpp:165-193) belongs to the tracker and is left
+to the caller: `loops` records every closure.  Keyframe features are those of the keyframe's own extraction, with the
 outlier flags all clear (the reference reads the flags its tracking left; DESIGN.md deviations), and
 the pose graph owns its RNG / RansacSE3 sticky state (the reference shares the process-global ones
 with the tracking thread).
@@ -21,6 +28,8 @@ import numpy as np
 
 MIN_T, MIN_R = 0.20, 0.1745          # Tracking::needKeyFrame (:217-218)
 RADIUS, MATCHES_TH = 0.50, 30        # PoseGraph::nearestNodes / createLocalEdges (:130, :160)
+LOOP_GAP, LOOP_INTERVAL, LEVELSUP = 15, 10, 4   # detectLoop (:250), LoopDetector's interval, computeBoW's levelsup
+LOOP_ITERATIONS = 20                 # PoseGraph::run (:71)
 INFO, HUBER = 100.0, 1.0             # EdgeSE3 information 100 I, RobustKernelHuber() delta 1 (:203-204)
 
 
@@ -77,9 +86,24 @@ def select_keyframes(poses):
 
 
 class PoseGraph:
-    def __init__(self, pkg, ctx=None, seed: int = 0):
+    def __init__(self, pkg, ctx=None, seed: int = 0, vocabulary=None, mean_inliers: int = 0):
+        """vocabulary: a vocabulary.Vocabulary enables loop detection (it is uploaded to ctx, whose loop database
+        this graph then owns); mean_inliers: Tracking::getMeanInliers(), the tracker's running mean."""
         self.pkg = pkg
         self.ctx = ctx                      # device Matcher + RansacSE3 for local edges (None: no local edges)
+        self.vocabulary = vocabulary
+        self.mean_inliers = int(mean_inliers)
+        self.kfs_from_last_loop = 0         # mnKFsFromLastLoop(0) (:45)
+        self.connections = {}               # id -> connected ids (Frame::addConnection)
+        self.entry_kf = []                  # loop-database entry -> keyframe id
+        self.loops = []                     # (cur, kf) of every detected loop
+        self.loop_attempts = []             # (kf, cur, matches, th, RansacSE3 result or None)
+        self.loop_queries = []              # (cur, candidate keyframe ids) of every obtainCandidates
+        if vocabulary is not None:
+            if ctx is None:
+                raise ValueError("PoseGraph: loop detection needs a device context")
+            ctx.voc_set(vocabulary)
+            ctx.loopdb_clear()
         h = C.c_void_p()
         self._check(pkg.lib().rgbd_pg_create(C.byref(h)), "rgbd_pg_create")
         self._h = h
@@ -120,6 +144,8 @@ class PoseGraph:
             Zp = Zm.ctypes.data
         self._check(self.pkg.lib().rgbd_pg_add_edge(self._h, frm, to, Zp, INFO, HUBER, C.byref(chi2)), "add_edge")
         self.edges.append((frm, to, None if Z is None else np.array(Z, np.float64)))
+        self.connections.setdefault(frm, set()).add(to)              # addConnection, both ways
+        self.connections.setdefault(to, set()).add(frm)
         return chi2.value
 
     def exist_edge(self, a: int, b: int) -> bool:
@@ -147,15 +173,71 @@ class PoseGraph:
         self._check(self.pkg.lib().rgbd_pg_vertex(self._h, kid, Twc.ctypes.data), "vertex")
         return np.linalg.inv(Twc.reshape(4, 4)).astype(np.float32)
 
-    # ---- PoseGraph::updateGraph without loop detection
+    # ---- PoseGraph::insertKeyFrame + updateGraph, then run()'s detectLoop / optimize(20)
     def insert_keyframe(self, kid: int, Tcw, xyz=None, desc=None):
+        """kid is the keyframe's frame id (LoopDetector's interval compares frame ids).  True when a loop closed."""
+        self.kfs_from_last_loop += 1                                   # insertKeyFrame (:295)
+        self.kf[kid] = dict(Tcw=np.asarray(Tcw, np.float32), xyz=xyz, desc=desc)
+        loops = self.vocabulary is not None and desc is not None and xyz is not None
+        if loops:
+            bow = self.ctx.bow_transform(desc, LEVELSUP)              # Frame::computeBoW (Core/Frame.cpp:243-249)
+            self.kf[kid]["bow"] = bow
+            self.kf[kid]["entry"] = self.ctx.loopdb_add(bow["ids"], bow["vals"])   # LoopDetector::add
+            self.entry_kf.append(kid)
         self.add_vertex(kid, Tcw, fixed=(kid == 0))                   # createNode
         if self.ref is not None:
             self.add_edge(kid, self.ref)                               # createEdgeWithReference
-        self.kf[kid] = dict(Tcw=np.asarray(Tcw, np.float32), xyz=xyz, desc=desc)
         if self.ctx is not None and xyz is not None:
             self._local_edges(kid)
         self.ref = kid
+        if loops and self.detect_loop():
+            self.optimize(LOOP_ITERATIONS)
+            return True
+        return False
+
+    def obtain_candidates(self, cur: int):
+        """LoopDetector::obtainCandidates(cur): keyframe ids, in the reference's order."""
+        conn = sorted(k for k in self.connections.get(cur, ()) if k != cur and "entry" in self.kf[k])
+        if not conn:
+            return []
+        bow = self.kf[cur]["bow"]
+        rev, _, _ = self.ctx.loopdb_query(bow["ids"], bow["vals"], query_first=False)   # score(pKFi, pKF) (:43)
+        min_score = min(float(rev[self.kf[k]["entry"]]) for k in conn)
+        score, shared, first = self.ctx.loopdb_query(bow["ids"], bow["vals"], query_first=True)   # (:70)
+        skip = np.zeros(len(score), np.uint8)
+        skip[[self.kf[k]["entry"] for k in conn] + [self.kf[cur]["entry"]]] = 1
+        got = self.pkg.loop_candidates(score, shared, first, self.entry_kf, skip, cur, min_score, LOOP_INTERVAL)
+        return [self.entry_kf[e] for e in got]
+
+    def detect_loop(self) -> bool:
+        """PoseGraph::detectLoop for the keyframe inserted last."""
+        cur = self.ref
+        if self.vocabulary is None or cur is None or "entry" not in self.kf[cur] or self.kfs_from_last_loop < LOOP_GAP:
+            return False
+        cands = self.obtain_candidates(cur)
+        self.loop_queries.append((cur, list(cands)))
+        c = self.kf[cur]
+        th = int(float(self.mean_inliers) * 0.20)                      # uint th = double(getMeanInliers()) * 0.20
+        prm = self.pkg.ransac_params(200, th, 3.0, 4)
+        for kid in cands:
+            if self.exist_edge(cur, kid):
+                continue
+            k = self.kf[kid]
+            m = self.ctx.match(k["desc"], c["desc"], np.zeros(len(k["desc"]), np.uint8), k["xyz"][:, 2], c["xyz"][:, 2], 0.9)
+            if len(m) < th:
+                self.loop_attempts.append((kid, cur, m, th, None))
+                continue
+            ok, T21, inl, rmse = self.ctx.ransac_se3(k["xyz"], c["xyz"], m, prm, self.rng, self.sticky)
+            self.loop_attempts.append((kid, cur, m, th, dict(ok=ok, T21=T21.copy(), inliers=inl, rmse=rmse,
+                                                             rng=list(self.rng.state) + [self.rng.f, self.rng.r],
+                                                             sticky=(self.sticky.cov, self.sticky.set))))
+            if not ok:
+                continue
+            self.add_edge(cur, kid, T21.astype(np.float64))          # createEdge(pKF, toIsometry3d(mT21))
+            self.kfs_from_last_loop = 0
+            self.loops.append((cur, kid))
+            return True
+        return False
 
     def _centre(self, kid):
         T = self.kf[kid]["Tcw"].astype(np.float64)
@@ -217,15 +299,17 @@ def corrected_trajectory(poses, kfs, kf_poses):
 
 
 def posegraph_sequence(pkg, get_frame, camera: dict, poses, nfeatures: int = 1000, iterations: int = 10,
-                       device: int = 0, W: int = 640, H: int = 480, record: dict | None = None):
+                       device: int = 0, W: int = 640, H: int = 480, record: dict | None = None, vocabulary=None,
+                       mean_inliers: int = 0):
     """The PoseGraph thread over a tracked sequence: keyframes by Tracking::needKeyFrame, each inserted
     with its own features (extracted again on the device: rgbd_frame), local edges by the device
     Matcher + RansacSE3, then PoseGraph::shutdown's optimize(); returns the corrected trajectory
-    (saveCameraTrajectory re-anchoring), the keyframe ids and (vertices, edges, chi2 before, chi2 after)."""
+    (saveCameraTrajectory re-anchoring), the keyframe ids and (vertices, edges, chi2 before, chi2 after).
+    vocabulary / mean_inliers: loop detection as PoseGraph's (record gains `loops`)."""
     c = pkg.camera(camera["fx"], camera["fy"], camera["cx"], camera["cy"], camera["k1"], camera["k2"],
                    camera["p1"], camera["p2"], camera["k3"], camera["factor"])
     ctx = pkg.Context(W, H, max_batch=1, orb=pkg.orb_params(nfeatures), cam=c, device=device)
-    g = PoseGraph(pkg, ctx)
+    g = PoseGraph(pkg, ctx, vocabulary=vocabulary, mean_inliers=mean_inliers)
     try:
         kfs = select_keyframes(poses)
         for k in kfs:
@@ -237,7 +321,7 @@ def posegraph_sequence(pkg, get_frame, camera: dict, poses, nfeatures: int = 100
         if record is not None:   # the graph as built (parity tests): vertices (Twc), edges, local-edge attempts
             record.update(vertices={k: g.vertex_twc(k) for k in kfs},
                           edges=list(g.edges), attempts=list(g.attempts),
-                          features={k: dict(g.kf[k]) for k in kfs})
+                          features={k: dict(g.kf[k]) for k in kfs}, loops=list(g.loops))
         res = g.optimize(iterations)
         chi_after = res[0] if res else chi_before
         kf_poses = {k: g.kf[k]["Tcw"] for k in kfs}
