@@ -1,5 +1,5 @@
 // blur_tab.h -- operand tables of the level blur on the matrix cores (k_fast's blur_tile_walk, extract.hip).
-// Host only, no HIP dependency: api.cpp builds the tables, tests/blur_tab_check.cpp emulates the products.
+// Host only, no HIP dependency: geometry.cpp builds the tables, tests/blur_tab_check.cpp emulates the products.
 //
 // The 7x7 level blur (kernel {18,34,49,54,49,34,18}/256 both ways, BORDER_REFLECT_101, ufixedpoint16) of a
 // 32 x 32 output tile is two products of v_mfma_i32_32x32x32_i8, each K = 64 (two MFMAs):

@@ -34,11 +34,9 @@ struct OutBufs {   // one owned set
 struct rgbd_ctx {
     int device = 0;
     int W = 0, H = 0, maxB = 0;
-    rgbd_orb_params orb{};
     rgbd_camera cam{};
-    rgbd::ExtractCfg cfg{};              // host copy
-    std::vector<rgbd::Cell> cells;
-    std::vector<rgbd::FastSeg> segs;     // k_fast segments (per level: gathered leftovers, then full cell-row runs)
+    rgbd::ExtractCfg cfg{};              // host copy of the geometry (geometry.cpp); its tables live on the device only
+    int n_segs = 0;                      // k_fast segments per frame (d_segs)
     std::string err;
 
     hipStream_t stream = nullptr;        // launch stream (own or external)

@@ -24,6 +24,7 @@
 
 #include "rgbd_internal.h"
 #include "blur_tab.h"
+#include "dist_layout.h"
 #include "undistort_dev.h"
 #include "wave_dev.h"
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void k_gray(const uint8_t* __restrict__ bgr, u
 // ------------------------------------------------------------------ resize (:786-790)
 // OpenCV 3.4 INTER_LINEAR 8U: horizontal int taps (11-bit weights); vertical pass = SSE2
 // VResizeLinearVec_32s8u arithmetic on [0, rs_simd), FixedPtCast<int,uchar,22> on the tail.
-// cv::resize INTER_LINEAR tables (api.cpp resize_tables, the same float / double operations)
+// cv::resize INTER_LINEAR tables (geometry.cpp resize_tables, the same float / double operations)
 __device__ __forceinline__ ResizeX resize_xt(int dx, double scale_x, int sw)
 {
     float fx = (float)((dx + 0.5) * scale_x - 0.5);
@@ -796,7 +797,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RGBD_FAST_WP
         // pack_key(x, y, m - 1) = ((m - 1) << 22) + (x | y << 11): the survivor's m is the low (A) or high (B)
         // half of Mr, shifted left by 22 (m < 256).  No capacity test: NMS survivors are strict maxima over
         // their 8 neighbours, so no two are adjacent, and an independent set of the king graph on an a x b
-        // interior holds at most ceil(a/2) ceil(b/2) corners, which is how the host sizes cell_cap (api.cpp)
+        // interior holds at most ceil(a/2) ceil(b/2) corners, which is how the host sizes cell_cap (geometry.cpp)
         const uint32_t ms = fA ? Mr : (Mr >> 16);
         const uint32_t key = (ms << 22) + (xy0B - (fA ? 1u : 0u)) + (((uint32_t)r << 11) - (1u << 22));
         if (f) *reinterpret_cast<uint32_t*>(slots_b + 4u * slot) = key;
@@ -1131,14 +1132,7 @@ struct DistState<false> {
     __device__ __forceinline__ int node_of(int k) const { return st[k] >> 2; }
 };
 
-// LDS of k_distribute's node arrays, before the key region (16-byte aligned for the keys' 128-bit reads):
-// sortkey 8NC + childcnt x2 32NC + tmp/tmp2 8SC + size/cid A,B 16NC + best 4NC + dest 8NC + ord 2NC + bbox A,B 16NC
-__host__ __device__ constexpr size_t dist_node_bytes(int NC, int SC)
-{
-    return (((size_t)NC * 86 + (size_t)SC * 8) + 15) & ~(size_t)15;
-}
-// ... and of the key region for kc keys (kc a multiple of 16): the u32 keys + their state
-__host__ __device__ constexpr size_t dist_key_bytes(int kc, bool u8) { return (size_t)kc * 4 + (size_t)(kc >> 2) * (u8 ? 5 : 8); }
+// (k_distribute's LDS: the node arrays, dist_node_bytes, then the key region, dist_key_bytes -- dist_layout.h)
 
 // One-root levels, pyramid path.  quad_of and the child boxes split x and y separately, and a midpoint depends on
 // its own interval alone, so a node at depth d is a pair (ix, iy) of d-bit paths in two 1-D interval trees over
@@ -2493,19 +2487,6 @@ hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* seg
     else
         return dispatch(k_fast, dim3(nbb + nseg, B), dim3(64), 0, st, pyr, cells, segs, d_cfg, nseg, cell_count,
                            cell_slots, 0, blur, nbb, blur_tab, blur_waves);
-}
-
-size_t distribute_lds_bytes(int NC, int SC)
-{
-    return dist_node_bytes(NC, SC) + 64;   // the node arrays + the kernel's static LDS
-}
-
-int distribute_key_capacity(long room, int NC)
-{
-    // per group of four keys: 16 bytes of keys + their state (u8 node ids + 2-bit quadrants: 5 bytes; u16: 8);
-    // a multiple of 16 keys keeps the quadrant plane whole dwords
-    const int per4 = 16 + (NC <= 256 ? 5 : 8);
-    return room > 0 ? (int)(room / per4 * 4 / 16 * 16) : 0;
 }
 
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,

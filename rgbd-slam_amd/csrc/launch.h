@@ -19,9 +19,6 @@ hipError_t launch_fast(const uint8_t* pyr, const Cell* cells, const FastSeg* seg
 hipError_t launch_distribute(const int* cell_count, const uint32_t* cell_slots, const ExtractCfg* d_cfg, int node_cap,
                        int scan_cap, int l0, int nlv, int kc, uint32_t* keys, uint16_t* node, int* sel_count,
                        uint32_t* sel, int* err, uint8_t* path, int B, hipStream_t st);
-size_t distribute_lds_bytes(int node_cap, int scan_cap);
-// keys per level (a multiple of 16) whose round state fits in room bytes of LDS beside the node arrays
-int distribute_key_capacity(long room, int node_cap);
 hipError_t launch_undistort(const uint16_t* depth, const int* counts, const ExtractCfg* d_cfg, int kp_cap, const float* kps,
                       float* kun, float* xyz, int B, hipStream_t st);
 // sel_count holds selc_elems counts: at least sel_count_elems(B, nlevels) (rgbd_internal.h), else hipErrorInvalidValue

@@ -4,7 +4,15 @@
 // float/double semantics and passed to kernels by value (kernel-argument SGPRs), so
 // the kernels never re-derive a float-rounded size or budget.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+// host-only translation units (geometry.cpp, the check programs under tests/) include this header without HIP
+#ifdef __HIPCC__
+#define RGBD_HD __host__ __device__
+#else
+#define RGBD_HD
+#endif
 
 namespace rgbd {
 
@@ -22,6 +30,7 @@ constexpr int kPyrThreads = RGBD_PYR_THREADS;  // k_pyramid: threads per strip w
 constexpr int kPyrStrips = RGBD_PYR_STRIPS;  // k_pyramid: horizontal strips per frame (one workgroup each; 10 / 12 / 16 ->
                                              // 3.685-3.697 / 3.695-3.701 / 3.664-3.669 ms per step: a 16th of 640 x 480 is
                                              // 39 KB of LDS, four workgroups per CU, profiles/blur_level0)
+constexpr int kPyrLdsLimit = 150 * 1024;     // k_pyramid: most LDS a strip workgroup may ask for (level buffers + resize rows)
 #define RGBD_BLUR_TH 48   // r04 (level blur of levels 1-7 in the k_fast grid): 16 / 32 / 48 rows -> 230.5k / 232.6k / 233.3k frames/s (profiles/r04_ab_blur_rows)
 constexpr int kBlurTH = RGBD_BLUR_TH;        // level blur: rows per strip (one thread per 4-px column quad)
 // bench.py's --full byte model (its PB_LEVELS, held to this line by tests/test_abi.py) charges the blurred bytes of
@@ -161,9 +170,9 @@ struct ResizeY { int16_t sy0, sy1, b0, b1; };  // clipped source rows + ibeta
 
 // packed candidate / selected keypoint: x (11 bits) | y (11 bits) | score (8 bits), coords
 // relative to (minBorderX, minBorderY) of the level
-__host__ __device__ inline uint32_t pack_key(int x, int y, int s) { return (uint32_t)x | ((uint32_t)y << 11) | ((uint32_t)s << 22); }
-__host__ __device__ inline int key_x(uint32_t k) { return (int)(k & 2047u); }
-__host__ __device__ inline int key_y(uint32_t k) { return (int)((k >> 11) & 2047u); }
-__host__ __device__ inline int key_s(uint32_t k) { return (int)(k >> 22); }
+RGBD_HD inline uint32_t pack_key(int x, int y, int s) { return (uint32_t)x | ((uint32_t)y << 11) | ((uint32_t)s << 22); }
+RGBD_HD inline int key_x(uint32_t k) { return (int)(k & 2047u); }
+RGBD_HD inline int key_y(uint32_t k) { return (int)((k >> 11) & 2047u); }
+RGBD_HD inline int key_s(uint32_t k) { return (int)(k >> 22); }
 
 }  // namespace rgbd
