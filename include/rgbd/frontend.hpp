@@ -11,6 +11,7 @@
 //   rgbd::PnPRansac      <- PnPRansac::compute                             Solver/PnPRansac.h
 //   rgbd::Vocabulary     <- DBoW3::Vocabulary (transform, score, size; TF_IDF + L1_NORM)  Core/Frame.cpp:243-249
 //   rgbd::LoopDetector   <- LoopDetector::add / obtainCandidates            PlaceRecognition/LoopDetector.cpp:22-84
+//   rgbd::OctomapDrawer  <- OctomapDrawer::reset / insertCloud + the leaves render draws  Drawer/OctomapDrawer.cpp:15-79
 //
 // No OpenCV/Eigen types: poses are row-major float[16] (cv::Mat 4x4 CV_32F layout), keypoints and
 // matches are the byte-identical rgbd_keypoint / rgbd_dmatch.  INTEGRATION.md shows the thin
@@ -354,6 +355,16 @@ public:
     {
         if (mBowVec.empty()) voc.transform(mDescriptors.data(), N, mBowVec, mFeatVec, 4);
     }
+    // Tracking::createKeyFrame's cloud (System/Tracking.cpp:234-237) from the keyframe's own images, camera frame
+    void createFilteredCloud(const ExtractorBase& ex, const uint8_t* bgr, const uint16_t* depth)
+    {
+        const rgbd_cloud_params prm{6, 0.5f, 4.0f, 0.04f, 50, 1.0};
+        mCloud.resize(16384);
+        int32_t n = 0;
+        check(ex.ctx(), rgbd_keyframe_cloud(ex.ctx(), bgr, depth, &prm, mCloud.data(), (int32_t)mCloud.size(), &n), "createFilteredCloud");
+        mCloud.resize((size_t)n);
+    }
+    bool isValidCloud() const { return !mCloud.empty(); }
     int id() const { return mnId; }
     static int& nextId() { static int next = 0; return next; }      // Frame::nNextId
     // connections are kept as plain pointers: the map that owns the keyframes outlives them
@@ -377,6 +388,62 @@ public:
     FeatureVector mFeatVec;
     double mScore = 0.0;
     std::set<Frame*> mspConnectedKFs;
+    std::vector<rgbd_point> mCloud;         // mpCloud: the keyframe's filtered cloud (createFilteredCloud)
+};
+
+// OctomapDrawer over a device-resident occupancy map on the extractor's context: insertCloud is Frame::updateSensor
+// (rgbd_occmap_sensor_pose) plus one scan of the keyframe's cloud; leaves is the query render draws from.  The leaves
+// only: no inner nodes, no .ot file, no GL (DESIGN.md "Occupancy map definition"; parity with liboctomap is unpinned).
+class OctomapDrawer {
+public:
+    explicit OctomapDrawer(rgbd_ctx* ctx, int64_t capacity = (int64_t)1 << 20) : ctx_(ctx)
+    {
+        const rgbd_occmap_params prm{0.08, 0.9, 0.4, 0.001, 0.999, capacity};   // OctomapDrawer::reset's values
+        check(ctx_, rgbd_occmap_create(ctx_, &prm, &map_), "OctomapDrawer");
+    }
+    ~OctomapDrawer() { rgbd_occmap_destroy(map_); }
+    OctomapDrawer(const OctomapDrawer&) = delete;
+    OctomapDrawer& operator=(const OctomapDrawer&) = delete;
+    void reset()
+    {
+        msIdxs.clear();
+        check(ctx_, rgbd_occmap_clear(map_), "OctomapDrawer::reset");
+    }
+    // a keyframe id is inserted once; a cloud that does not fit the table throws and leaves the map as it was
+    void insertCloud(Frame& KF, double maxRange = -1.0)
+    {
+        if (msIdxs.count(KF.id()) > 0) return;
+        float Twc34[12], origin[3];
+        if (rgbd_occmap_sensor_pose(KF.getPose().data(), Twc34, origin) != RGBD_OK) throw Error("OctomapDrawer::insertCloud: pose not finite");
+        check(ctx_, rgbd_occmap_insert(map_, KF.mCloud.data(), (int32_t)KF.mCloud.size(), Twc34, origin, maxRange), "OctomapDrawer::insertCloud");
+        msIdxs.insert(KF.id());
+    }
+    size_t size() const
+    {
+        int64_t n = 0;
+        check(ctx_, rgbd_occmap_size(map_, &n), "OctomapDrawer::size");
+        return (size_t)n;
+    }
+    // the leaves with occupancy >= minOccupancy (render's occThresh is 0.9; <= 0: all), ascending by key
+    size_t leaves(std::vector<uint16_t>& keys, std::vector<float>& logodds, std::vector<uint8_t>& rgb, double minOccupancy = 0.0) const
+    {
+        const float lo = minOccupancy > 0.0 ? (float)std::log(minOccupancy / (1.0 - minOccupancy)) : -std::numeric_limits<float>::infinity();
+        const size_t cap = std::max<size_t>(size(), 1);
+        keys.resize(3 * cap);
+        logodds.resize(cap);
+        rgb.resize(3 * cap);
+        int64_t n = 0;
+        check(ctx_, rgbd_occmap_leaves(map_, lo, keys.data(), logodds.data(), rgb.data(), (int64_t)cap, &n), "OctomapDrawer::leaves");
+        keys.resize(3 * (size_t)n);
+        logodds.resize((size_t)n);
+        rgb.resize(3 * (size_t)n);
+        return (size_t)n;
+    }
+
+private:
+    rgbd_ctx* ctx_;
+    rgbd_occmap* map_ = nullptr;
+    std::set<int> msIdxs;
 };
 
 // LoopDetector over the context's keyframe database: add uploads the keyframe's BoW vector; obtainCandidates scores

@@ -617,6 +617,49 @@ rgbd_status rgbd_loop_candidates(int32_t n, const double* score, const int32_t* 
                                  const int32_t* frame_id, const uint8_t* skip, int32_t query_id, double min_score,
                                  int32_t interval, int32_t* out, int32_t* n_out);
 
+/* ------------------------------------------------------------------ coloured occupancy map */
+/* octomap::ColorOcTree as OctomapDrawer drives it (Drawer/OctomapDrawer.cpp:15-79; MapDrawer::drawOctomap,
+ * Drawer/MapDrawer.cpp:48-71): every keyframe cloud is ray-cast into depth-16 voxels of `resolution` metres, each voxel
+ * updated once per scan (occupied beats free), then coloured by the scan's points in cloud order.  octomap is absent: the
+ * operator is the definition in DESIGN.md "Occupancy map definition", written from the reference's caller and recalled
+ * octomap 1.9 semantics; parity with the library is unpinned.  Leaves only: no inner nodes, no pruning, no .ot file.
+ *
+ * The map is a device-resident open-addressing table of `capacity` voxels (a power of two) that belongs to the context
+ * it was created on, runs on that context's stream, and must be destroyed before it.  RGBD_ERR_UNSUPPORTED before any
+ * copy or launch: a null pointer, resolution <= 0 or not finite, a probability outside (0, 1), clamp_min >= clamp_max,
+ * capacity < 64, above 2^30 or no power of two, more than 16384 points in a scan, a pose or origin that is not finite, a
+ * maxrange that is NaN. */
+typedef struct rgbd_occmap rgbd_occmap;
+typedef struct {
+    double resolution;                                  /* OctomapDrawer::reset: 0.08 */
+    double prob_hit, prob_miss, clamp_min, clamp_max;   /* 0.9, 0.4, 0.001, 0.999; each becomes (float)log(p / (1 - p)) */
+    int64_t capacity;                                   /* voxels the table holds */
+} rgbd_occmap_params;
+rgbd_status rgbd_occmap_create(rgbd_ctx* ctx, const rgbd_occmap_params* prm, rgbd_occmap** map);
+void rgbd_occmap_destroy(rgbd_occmap* map);
+rgbd_status rgbd_occmap_clear(rgbd_occmap* map);
+rgbd_status rgbd_occmap_size(rgbd_occmap* map, int64_t* n);
+/* insertPointCloud(cloud, origin, maxrange) + the colour fold of one scan: n rgbd_points in the camera frame (what
+ * rgbd_keyframe_cloud* returns), Twc34 = the f32 [R' | Ow] (row-major 3x4) that takes them to the world on the device,
+ * origin = the sensor's position, maxrange < 0 = none.  Points that are not finite, before or after the transform, are
+ * skipped.  A scan whose voxels do not fit the table leaves the map exactly as it was: RGBD_ERR_CAPACITY. */
+rgbd_status rgbd_occmap_insert(rgbd_occmap* map, const rgbd_point* pts, int32_t n, const float* Twc34, const float* origin,
+                               double maxrange);
+/* nscan scans queued without a host round trip between them: scan k's points are pts[k * cap ...], counts[k] of them
+ * (rgbd_keyframe_cloud_batch's layout), its pose Twc34s[12 k ...] and origin origins[3 k ...].  The first scan that
+ * does not fit and every scan after it are not applied: *applied = the scans applied, RGBD_ERR_CAPACITY when fewer than
+ * nscan. */
+rgbd_status rgbd_occmap_insert_batch(rgbd_occmap* map, const rgbd_point* pts, const int32_t* counts, int32_t cap, int32_t nscan,
+                                     const float* Twc34s, const float* origins, double maxrange, int32_t* applied);
+/* Every leaf with log-odds >= min_logodds (-INFINITY: all), ascending by (kx << 32) | (ky << 16) | kz: keys[3 i ...] =
+ * (kx, ky, kz), logodds[i], rgb[3 i ...] = (r, g, b).  *n = the number of such leaves; above cap: RGBD_ERR_CAPACITY and
+ * nothing written.  keys / logodds / rgb may be NULL with cap = 0 to count. */
+rgbd_status rgbd_occmap_leaves(rgbd_occmap* map, float min_logodds, uint16_t* keys, float* logodds, uint8_t* rgb, int64_t cap,
+                               int64_t* n);
+/* Frame::updateSensor (Core/Frame.cpp:551-608), host only: from Tcw (row-major 4x4 f32) Rwc = Rcw^T and Ow = -Rcw^T tcw
+ * (double sums, one rounding), R' = Eigen::Quaternionf(Rwc).toRotationMatrix() in f32; Twc34 = [R' | Ow], origin = Ow. */
+rgbd_status rgbd_occmap_sensor_pose(const float* Tcw, float* Twc34, float* origin);
+
 /* ------------------------------------------------------------------ measurement */
 /* Per-kernel HIP-event timing on the context stream (off by default). */
 rgbd_status rgbd_set_timing(rgbd_ctx* ctx, int32_t enable);

@@ -12,6 +12,7 @@ that mirror the reference's operator surfaces for this path:
   Context.bow_transform(desc)      <- Frame::computeBoW            Core/Frame.cpp:243-249
   Context.loopdb_add / loopdb_query, loop_candidates <- LoopDetector  PlaceRecognition/LoopDetector.cpp:22-84
   RansacSE3(...).compute(F1, F2, m) <- RansacSE3::compute          Solver/SolverSE3.cpp:23-133
+  OccupancyMap(ctx).insert / insert_batch / leaves <- OctomapDrawer::insertCloud  Drawer/OctomapDrawer.cpp:38-79
 
 The GPU library is mandatory: there is no CPU fallback.  Importing works without a GPU
 (the library loads and exports its symbols); any compute call needs a HIP device and
@@ -140,6 +141,12 @@ class GicpParams(C.Structure):
                 ("gicp_epsilon", C.c_double), ("gn_iterations", C.c_int32), ("enable", C.c_int32)]
 
 
+class OccmapParams(C.Structure):
+    """rgbd_occmap_params: OctomapDrawer::reset's values (Drawer/OctomapDrawer.cpp:15-25) and the table's capacity."""
+    _fields_ = [("resolution", C.c_double), ("prob_hit", C.c_double), ("prob_miss", C.c_double),
+                ("clamp_min", C.c_double), ("clamp_max", C.c_double), ("capacity", C.c_int64)]
+
+
 _vp = C.c_void_p
 _i32 = C.c_int32
 _PI = C.POINTER(C.c_int32)
@@ -234,6 +241,14 @@ _SIGS = {
     "rgbd_keyframe_cloud": (_i32, [_vp, _vp, _vp, C.POINTER(CloudParams), _vp, _i32, _PI]),
     "rgbd_keyframe_cloud_f32": (_i32, [_vp, _vp, _vp, C.POINTER(CloudParams), _vp, _i32, _PI]),
     "rgbd_keyframe_cloud_batch": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, C.POINTER(CloudParams), _vp, _i32, _vp]),
+    "rgbd_occmap_create": (_i32, [_vp, C.POINTER(OccmapParams), C.POINTER(_vp)]),
+    "rgbd_occmap_destroy": (None, [_vp]),
+    "rgbd_occmap_clear": (_i32, [_vp]),
+    "rgbd_occmap_size": (_i32, [_vp, C.POINTER(C.c_int64)]),
+    "rgbd_occmap_insert": (_i32, [_vp, _vp, _i32, _vp, _vp, C.c_double]),
+    "rgbd_occmap_insert_batch": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_double, _PI]),
+    "rgbd_occmap_leaves": (_i32, [_vp, C.c_float, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "rgbd_occmap_sensor_pose": (_i32, [_vp, _vp, _vp]),
     "rgbd_pg_create": (_i32, [C.POINTER(_vp)]),
     "rgbd_pg_destroy": (None, [_vp]),
     "rgbd_pg_add_vertex": (_i32, [_vp, _i32, _vp, _i32]),
@@ -327,6 +342,18 @@ def umeyama_params(error_version=EUCLIDEAN_ERROR, used_pairs=3, min_matches=10, 
 def gicp_params(max_iterations=10, max_corr=0.07, gn_iterations=4, enable=True) -> GicpParams:
     """Tracking's GICP settings (System/Tracking.cpp:147-151) over the Gicp ctor (Solver/Gicp.cpp:12-15)."""
     return GicpParams(max_iterations, 20, max_corr, 1e-9, 2e-3, 1e-3, gn_iterations, int(enable))
+
+
+def occmap_params(resolution=0.08, prob_hit=0.9, prob_miss=0.4, clamp_min=0.001, clamp_max=0.999,
+                  capacity=1 << 20) -> OccmapParams:
+    """OctomapDrawer::reset (Drawer/OctomapDrawer.cpp:15-25); capacity = voxels the device table holds (a power of two)."""
+    return OccmapParams(resolution, prob_hit, prob_miss, clamp_min, clamp_max, capacity)
+
+
+def occmap_logodds(p: float) -> np.float32:
+    """(float)log(p / (1 - p)) with the f64 libm log, as the library converts its probabilities."""
+    import math
+    return np.float32(math.log(p / (1.0 - p)))
 
 
 def rng(seed: int) -> Rng:
@@ -1187,3 +1214,91 @@ class Context:
     def set_stream(self, stream: int):
         """Launch on a caller's HIP stream (a torch.cuda.Stream's .cuda_stream); 0 = the context's own."""
         self._check(lib().rgbd_set_stream(self._h, C.c_void_p(stream)), "set_stream")
+
+
+class OccupancyMap:
+    """The coloured occupancy map (rgbd_occmap_*): OctomapDrawer's ColorOcTree as a device-resident voxel table on
+    `ctx`'s stream.  Leaves only; the definition is DESIGN.md "Occupancy map definition" (parity with liboctomap is
+    unpinned)."""
+
+    def __init__(self, ctx: Context, prm: OccmapParams | None = None):
+        self.ctx = ctx   # the context must outlive the map
+        self.prm = prm or occmap_params()
+        h = C.c_void_p()
+        st = lib().rgbd_occmap_create(ctx._h, C.byref(self.prm), C.byref(h))
+        self._h = h
+        if st != 0:
+            raise RgbdError(f"occmap_create: {lib().rgbd_last_error(ctx._h).decode()} (status {st})")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            if self.ctx._h.value:
+                lib().rgbd_occmap_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st, what):
+        if st != 0:
+            raise RgbdError(f"{what}: {lib().rgbd_last_error(self.ctx._h).decode()} (status {st})")
+
+    @staticmethod
+    def _pose(Twc34, origin):
+        T = np.ascontiguousarray(Twc34, np.float32)
+        o = np.ascontiguousarray(origin, np.float32)
+        if T.size != 12 or o.size != 3:
+            raise ValueError("occmap: Twc34 is 3x4 and origin has 3 entries")
+        return T, o
+
+    def insert(self, pts, Twc34, origin, maxrange: float = -1.0):
+        """One scan: rgbd_point array in the camera frame, the f32 [R' | Ow] and the sensor origin (occmap.sensor_pose).
+        A scan that does not fit leaves the map as it was and raises (status 3)."""
+        pts = np.ascontiguousarray(pts, POINT_DTYPE)
+        T, o = self._pose(Twc34, origin)
+        self._check(lib().rgbd_occmap_insert(self._h, _ptr(pts), len(pts), _ptr(T), _ptr(o), float(maxrange)), "occmap_insert")
+
+    def insert_batch(self, clouds, Twc34s, origins, maxrange: float = -1.0) -> int:
+        """The scans of a list of clouds queued in one call; returns how many were applied (all, unless one did not fit:
+        that one and the scans after it are left out and nothing is raised)."""
+        n = len(clouds)
+        if n == 0:
+            return 0
+        cap = max(max(len(c) for c in clouds), 1)
+        pts = np.zeros((n, cap), POINT_DTYPE)
+        counts = np.zeros(n, np.int32)
+        for k, c in enumerate(clouds):
+            pts[k, :len(c)] = c
+            counts[k] = len(c)
+        T = np.ascontiguousarray(Twc34s, np.float32)
+        o = np.ascontiguousarray(origins, np.float32)
+        if T.size != 12 * n or o.size != 3 * n:
+            raise ValueError("occmap: one 3x4 pose and one origin per cloud")
+        applied = C.c_int32(0)
+        st = lib().rgbd_occmap_insert_batch(self._h, _ptr(pts), _ptr(counts), cap, n, _ptr(T), _ptr(o), float(maxrange),
+                                            C.byref(applied))
+        if st != 3:   # RGBD_ERR_CAPACITY is the count
+            self._check(st, "occmap_insert_batch")
+        return applied.value
+
+    def clear(self):
+        self._check(lib().rgbd_occmap_clear(self._h), "occmap_clear")
+
+    def __len__(self):
+        n = C.c_int64(0)
+        self._check(lib().rgbd_occmap_size(self._h, C.byref(n)), "occmap_size")
+        return n.value
+
+    def leaves(self, min_prob: float | None = None):
+        """(keys (n, 3) u16, logodds (n,) f32, rgb (n, 3) u8) of the leaves with occupancy >= min_prob (None: all),
+        ascending by (kx << 32) | (ky << 16) | kz."""
+        lo = np.float32(-np.inf) if min_prob is None else occmap_logodds(min_prob)
+        n = C.c_int64(0)
+        cap = max(len(self), 1)
+        keys, v, rgb = np.zeros((cap, 3), np.uint16), np.zeros(cap, np.float32), np.zeros((cap, 3), np.uint8)
+        self._check(lib().rgbd_occmap_leaves(self._h, C.c_float(lo), _ptr(keys), _ptr(v), _ptr(rgb), cap, C.byref(n)),
+                    "occmap_leaves")
+        return keys[:n.value].copy(), v[:n.value].copy(), rgb[:n.value].copy()

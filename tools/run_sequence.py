@@ -25,7 +25,12 @@ def main():
     ap.add_argument("--out", default="CameraTrajectory.txt")
     ap.add_argument("--posegraph", action="store_true",
                     help="keyframe pose graph (local edges on the device, host LM) and the corrected trajectory")
+    ap.add_argument("--occmap", metavar="FILE.npz", default=None,
+                    help="with --posegraph: the coloured occupancy map of the keyframes' clouds under their corrected "
+                         "poses (keys, probability, logodds, rgb, resolution)")
     args = ap.parse_args()
+    if args.occmap and not args.posegraph:
+        ap.error("--occmap needs --posegraph (the keyframes and their corrected poses)")
     from conftest import load_pkg
     import ate
     pkg = load_pkg()
@@ -42,6 +47,11 @@ def main():
         from rgbd_slam_amd.posegraph import posegraph_sequence
         poses, kfs, (v, e, c0, c1) = posegraph_sequence(pkg, ds.frame, ds.camera, poses, nfeatures=args.nfeatures)
         print(f"pose graph: {v} keyframes, {e} edges, chi2 {c0:.4g} -> {c1:.4g}")
+        if args.occmap:
+            from rgbd_slam_amd.occmap import occmap_sequence
+            keys, prob, lo, rgb = occmap_sequence(pkg, ds.frame, ds.camera, poses, kfs)
+            np.savez(args.occmap, keys=keys, probability=prob, logodds=lo, rgb=rgb, resolution=0.08)
+            print(f"occupancy map: {len(keys)} voxels of 0.08 m, {int((prob >= 0.9).sum())} at occupancy >= 0.9 -> {args.occmap}")
     elif "rel" in extras:   # solver se3: the poses saveCameraTrajectory composes (relative to the first keyframe)
         poses = DS.camera_trajectory_poses(extras["rel"], extras["keyframe"], poses)
     DS.write_tum_trajectory(args.out, ds.times[:n], poses)
