@@ -258,6 +258,11 @@ rgbd_status rgbd_pnp_ransac(rgbd_ctx* ctx, const float* p3, const float* p2, int
 rgbd_status rgbd_pnp_ransac_batch(rgbd_ctx* ctx, int32_t P, const int32_t* counts, const float* p3, const float* p2,
                                   const float* K4, const rgbd_pnp_params* prm, double* R9, double* t3,
                                   uint8_t* masks, int32_t* n_inliers, int32_t* iters_run, int32_t* ok);
+/* The hidden state of the solve's schedule, for tests: the RANSAC iterations per problem that the NEXT
+ * rgbd_pnp_ransac_batch (or tracking solve) evaluates in its first (k0) and second (k1) device chunk before the
+ * host continues -- 8 and 16 on a fresh context, afterwards what the previous solve's iteration counts set (4..64
+ * each).  Results do not depend on them (tests/test_gpu_pnp_edges.py).  No launch, no state change. */
+rgbd_status rgbd_debug_pnp_chunks(rgbd_ctx* ctx, int32_t* k0, int32_t* k1);
 
 /* PnPSolver::compute (Solver/PnPSolver.cpp:31-150): motion-only bundle adjustment of one pose from a guess and
  * 3D-2D matches -- one g2o SE(3) vertex, one EdgeSE3ProjectXYZOnlyPose per match under a Huber kernel, `rounds`

@@ -199,6 +199,7 @@ _SIGS = {
     "rgbd_pnp_ransac": (_i32, [_vp, _vp, _vp, _i32, _vp, C.POINTER(PnpParams), _vp, _vp, _vp, _PI, _PI, _PI]),
     "rgbd_pnp_ransac_batch": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(PnpParams), _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
+    "rgbd_debug_pnp_chunks": (_i32, [_vp, _PI, _PI]),
     "rgbd_pnp_track_batch": (_i32, [_vp, _vp, _vp, _i32, C.c_float, C.POINTER(PnpParams), _vp, _vp, _vp, _vp]),
     "rgbd_pnp_track_submit": (_i32, [_vp, _vp, _vp, _i32, C.c_float, C.POINTER(PnpParams)]),
     "rgbd_pnp_track_collect": (_i32, [_vp, _vp, _vp, _vp, _vp]),
@@ -1082,6 +1083,12 @@ class Context:
 
     def pnp_ransac(self, p3, p2, K4, prm: PnpParams | None = None):
         return self.pnp_ransac_batch([(p3, p2)], K4, prm)[0]
+
+    def debug_pnp_chunks(self):
+        """rgbd_debug_pnp_chunks: (k0, k1), the iterations per problem of the next solve's two device chunks."""
+        k0, k1 = C.c_int32(), C.c_int32()
+        self._check(lib().rgbd_debug_pnp_chunks(self._h, C.byref(k0), C.byref(k1)), "debug_pnp_chunks")
+        return k0.value, k1.value
 
     def pnp_track_batch(self, d_bgr: int, d_depth: int, B: int, nnratio: float, prm: PnpParams | None = None,
                         pose0=None):

@@ -32,7 +32,7 @@ namespace {
 // problems still running after both chunks cost a host round trip, so the chunks follow the data: after
 // every solve K0 = the 90th percentile of that solve's iteration counts + 1 and K0 + K1 = the 99th + 2,
 // K1 rounded up to a multiple of 4, both clamped to [kPnpChunkMin, kPnpChunkMax] (the results do not depend
-// on them).  Round 4: one adaptive chunk of the 99th percentile (~20 hypotheses per pair at B = 1024)
+// on them: tests/test_gpu_pnp_edges.py runs every hand-over under three schedules).  Round 4: one adaptive chunk of the 99th percentile (~20 hypotheses per pair at B = 1024)
 // evaluated ~4x the ~5 iterations a pair runs on average.
 constexpr int kPnpFirstChunk = 8, kPnpFirstChunk2 = 16;   // the first solve's chunks
 constexpr int kPnpChunkMin = 4, kPnpChunkMax = 64;
@@ -452,6 +452,14 @@ rgbd_status rgbd_pnp_ransac(rgbd_ctx* c, const float* p3, const float* p2, int32
                             int32_t* iters_run, int32_t* ok)
 {
     return rgbd_pnp_ransac_batch(c, 1, &count, p3, p2, K4, prm, R9, t3, mask, n_inliers, iters_run, ok);
+}
+
+rgbd_status rgbd_debug_pnp_chunks(rgbd_ctx* c, int32_t* k0, int32_t* k1)
+{
+    if (!c || !k0 || !k1) return RGBD_ERR_ARG;
+    *k0 = c->pnp_chunk > 0 ? c->pnp_chunk : kPnpFirstChunk;   // as pnp_sample_launch fixes them
+    *k1 = c->pnp_chunk2 > 0 ? c->pnp_chunk2 : kPnpFirstChunk2;
+    return RGBD_OK;
 }
 
 }  // extern "C"
