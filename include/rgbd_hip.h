@@ -140,7 +140,13 @@ rgbd_status rgbd_debug_dist_path(rgbd_ctx* ctx, int32_t b, int32_t level, int32_
  * per 5x5 cell, Features/SVOextractor.cpp:86-137), retainBest(nfeatures) (Features/Extractor.cpp:56-57) and
  * cv::xfeatures2d::BriefDescriptorExtractor (32 bytes).  A context created this way runs it behind every
  * extraction entry point (rgbd_detect_and_compute, rgbd_frame, rgbd_extract_batch, the tracking chains).
- * Keypoints: size 0, angle -1, response = Shi-Tomasi score, octave = pyramid level (scale 2^level). */
+ * Keypoints: size 0, angle -1, response = Shi-Tomasi score, octave = pyramid level (scale 2^level).
+ * Shapes: the context builds the ORB geometry (1000 features, scale 1.2, 8 levels) before the SVO one, so it
+ * inherits the ORB refusals (width a multiple of 16, every ORB level at least 48 px, the 48-px cell ROI rule,
+ * height at most about twice the width); on top of them nlevels 1..8, even level widths above the last level,
+ * at most 12288 grid cells (ceil(W / cell_size) * ceil(H / cell_size)) and sides of at most 2047 px, else
+ * RGBD_ERR_UNSUPPORTED.  threshold: corners are found at this barrier and scored as the reference scores them,
+ * max(m - 1, 20) (its score search starts at the literal 20, Features/SVOextractor.cpp:106-107). */
 typedef struct {
     int32_t nfeatures;   /* 1000 (Extractor::setParameters) */
     int32_t nlevels;     /* 8 (1..8) */

@@ -169,6 +169,7 @@ constexpr int kDetGW = kDetTW + 2 * kDetHx;         // 80 staged columns: x0-8 .
 constexpr int kDetGH = kDetTH + 2 * kDetHy;         // 42 staged rows: y0-5 .. y0+36
 constexpr int kDetSW = kDetTW + 4, kDetSH = kDetTH + 2;   // score map: the tile + 1-pixel ring, rows
                                                          // padded to a dword multiple (66 used of 68)
+constexpr int kSvoScoreFloor = 20;                  // fast_corner_score_10(..., 20, ...)'s bmin
 
 // m for two horizontally adjacent pixels at once (packed u16 lanes): max over the 16 ten-pixel arcs of
 // the ring of min(v - x) (darker) or min(x - v) (brighter), clamped to [0, 255] by saturation.  The
@@ -272,8 +273,11 @@ __global__ __launch_bounds__(256) void k_svo_detect(const uint8_t* __restrict__ 
         reinterpret_cast<uint4*>(PI)[i] = o;
     }
     __syncthreads();
-    // 2. score map over the tile + 1-pixel ring: S = m - 1 where m > barrier (a FAST-10 corner), else 0;
-    //    pixels outside the detector's domain [3, w-3) x [3, h-3) are never corners
+    // 2. score map over the tile + 1-pixel ring: S = max(m - 1, 20) where m > barrier (a FAST-10 corner), else
+    //    0.  The 20 is fast_corner_score_10's bmin, a literal of the reference and not the barrier
+    //    (Features/SVOextractor.cpp:106-107): its search never tests bmin, so below a barrier of 20 every
+    //    weaker corner scores 20; at 20 and above the maximum changes nothing.  Pixels outside the detector's
+    //    domain [3, w-3) x [3, h-3) are never corners
     for (int task = tid; task < kDetSH * ((kDetTW + 2) / 2); task += 256) {
         const int sr = task / ((kDetTW + 2) / 2), cp = task - sr * ((kDetTW + 2) / 2);
         const int ty = sr - 1, tx = 2 * cp - 1;   // tile coordinates of the pair's first pixel
@@ -284,7 +288,7 @@ __global__ __launch_bounds__(256) void k_svo_detect(const uint8_t* __restrict__ 
             const int X = x0 + tx + k;
             const int mv = m[k];
             const bool dom = X >= 3 && X < w - 3 && Y >= 3 && Y < h - 3;
-            S[sr * kDetSW + 2 * cp + k] = (uint8_t)((dom && mv > cfg.barrier) ? mv - 1 : 0);
+            S[sr * kDetSW + 2 * cp + k] = (uint8_t)((dom && mv > cfg.barrier) ? max(mv - 1, kSvoScoreFloor) : 0);
         }
     }
     __syncthreads();
