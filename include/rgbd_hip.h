@@ -173,6 +173,59 @@ rgbd_status rgbd_svo_debug_grid(rgbd_ctx* ctx, int32_t b, int32_t* xyl, float* r
 rgbd_status rgbd_svo_retain_best(rgbd_ctx* ctx, const float* resp, int32_t n, int32_t n_points, int32_t depth_limit,
                                  int32_t* order, int32_t* m);
 
+/* ------------------------------------------------------------------ adaptive FAST + BRIEF extractor */
+/* Extractor(FAST, BRIEF, ADAPTIVE) (Features/Extractor.cpp:24-61, 82-109): DetectorAdjuster ->
+ * VideoDynamicAdaptedFeatureDetector -> VideoGridAdaptedFeatureDetector.  The frame is split into
+ * grid_rows x grid_cols cells widened by edge_threshold; each cell runs cv::FAST on its ROI at its own
+ * threshold (int)thresh, a double it carries from frame to frame and scales by `decrease` / `increase`
+ * until the cell yields gridMin..gridMax corners (at most `iterations` tries), keeps its maxPerCell
+ * strongest (std::nth_element at begin + maxPerCell), and the concatenated cells go through
+ * retainBest(nfeatures) and cv::xfeatures2d::BriefDescriptorExtractor (32 bytes).  With maxFeatures =
+ * (int)(min_features * 1.7): gridMin = round(min_features / (float)cells), gridMax = round(maxFeatures /
+ * (float)cells), maxPerCell = maxFeatures / cells.  Keypoints: size 7, angle -1, response = the FAST score,
+ * octave 0.  DESIGN.md, "Adaptive FAST + BRIEF definition".
+ * The per-cell thresholds are the context's state: an extraction of B frames walks them through the frames
+ * in order, and the next extraction starts where it ended (rgbd_adaptive_get / set_thresholds, _rewind).
+ * Shapes: the refusals of a one-level ORB geometry (width a multiple of 16 and at least 64, the 48-px cell ROI
+ * rule at level 0), sides of at most 2047 px, and RGBD_ERR_UNSUPPORTED
+ * before any allocation unless 1 <= min_thresh <= init_thresh <= max_thresh <= 1e9, 0 < decrease < 1 <
+ * increase, iterations in 1..32, a grid of 1..8 x 1..8, edge_threshold >= 0, every cell ROI at least 7 x 7,
+ * 1 <= maxPerCell, maxFeatures <= 12288, nfeatures >= 0 and 1 <= cell_cap <= 12288. */
+typedef struct {
+    int32_t nfeatures;        /* 1000: retainBest(nfeatures) (Extractor::setParameters) */
+    int32_t min_features;     /* 600 */
+    int32_t grid_rows, grid_cols;   /* 3, 3 */
+    int32_t edge_threshold;   /* 31: the cells' overlap margin */
+    int32_t iterations;       /* 5: tries per cell and frame */
+    int32_t cell_cap;         /* stored strict maxima per (frame, cell); 0: 8192.  A cell with more maxima at the
+                                 threshold it used than were stored fails that frame with RGBD_ERR_CAPACITY */
+    int32_t pad;
+    double init_thresh;       /* 20 */
+    double min_thresh;        /* 2 (>= 1) */
+    double max_thresh;        /* 10000 */
+    double increase;          /* 1.3 */
+    double decrease;          /* 0.7 */
+} rgbd_adaptive_params;
+rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batch, const rgbd_adaptive_params* params,
+                                 const rgbd_camera* cam, rgbd_ctx** out);
+/* The cells' thresholds (grid_rows * grid_cols doubles, row-major), after the last extraction / for the next. */
+rgbd_status rgbd_adaptive_get_thresholds(rgbd_ctx* ctx, double* thresh);
+rgbd_status rgbd_adaptive_set_thresholds(rgbd_ctx* ctx, const double* thresh);
+/* The next extraction starts from the thresholds in force before frame last_B - k of the last batch
+ * (1 <= k <= last_B): a device-to-device copy queued on the context's stream, for batches that overlap by
+ * k frames.  No host round trip. */
+rgbd_status rgbd_adaptive_rewind(rgbd_ctx* ctx, int32_t k);
+/* Cell `cell` of frame b of the last batch: the threshold before the frame (the double's bits), the integer
+ * threshold of its last try, the number of tries, and the corners of that try in raster order as
+ * (x, y, score) in ROI coordinates (what cv::FAST returned, before keepStrongest). */
+rgbd_status rgbd_adaptive_debug_cell(rgbd_ctx* ctx, int32_t b, int32_t cell, uint64_t* thresh_before_bits,
+                                     int32_t* thresh_used, int32_t* tries, int32_t* xys, int32_t cap, int32_t* n);
+/* The device keepStrongest (std::nth_element(begin, begin + N, end, response >) restated, k_adp_select's
+ * code) on n host responses (n <= 12288): order[0..min(n, N)) = the kept original indices in libstdc++'s
+ * order.  depth_limit as for rgbd_svo_retain_best. */
+rgbd_status rgbd_adaptive_keep_strongest(rgbd_ctx* ctx, const float* resp, int32_t n, int32_t N, int32_t depth_limit,
+                                         int32_t* order);
+
 /* ------------------------------------------------------------------ matching */
 /* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}.
  * At most 65536 train rows (nt): the kernel's rank key holds the train index in 16 bits.  A larger nt

@@ -67,6 +67,24 @@ def svo_params(nfeatures=1000, nlevels=8, cell_size=5, threshold=20, max_keypoin
     return SvoParams(nfeatures, nlevels, cell_size, threshold, max_keypoints)
 
 
+class AdaptiveParams(C.Structure):
+    """rgbd_adaptive_params: Extractor(FAST, BRIEF, ADAPTIVE) (Features/Extractor.cpp:82-109)."""
+    _fields_ = [("nfeatures", C.c_int32), ("min_features", C.c_int32), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32),
+                ("edge_threshold", C.c_int32), ("iterations", C.c_int32), ("cell_cap", C.c_int32), ("pad", C.c_int32),
+                ("init_thresh", C.c_double), ("min_thresh", C.c_double), ("max_thresh", C.c_double),
+                ("increase", C.c_double), ("decrease", C.c_double)]
+
+
+def adaptive_params(nfeatures=1000, min_features=600, grid_rows=3, grid_cols=3, edge_threshold=31, iterations=5,
+                    init_thresh=20.0, min_thresh=2.0, max_thresh=10000.0, increase=1.3, decrease=0.7,
+                    cell_cap=0) -> AdaptiveParams:
+    """The reference's values: setParameters(1000, ...), DetectorAdjuster(FAST, 20, 2, 10000, 1.3, 0.7), 600
+    minimum features, 5 iterations, a 3 x 3 grid with edge threshold 31; cell_cap 0 = 8192 stored maxima
+    per cell (a cell with more at the threshold it used raises RGBD_ERR_CAPACITY for that frame)."""
+    return AdaptiveParams(nfeatures, min_features, grid_rows, grid_cols, edge_threshold, iterations, cell_cap, 0,
+                          init_thresh, min_thresh, max_thresh, increase, decrease)
+
+
 class CloudParams(C.Structure):
     _fields_ = [("stride", C.c_int32), ("zmin", C.c_float), ("zmax", C.c_float), ("leaf", C.c_float),
                 ("sor_k", C.c_int32), ("sor_std", C.c_double)]
@@ -160,6 +178,13 @@ _SIGS = {
     "rgbd_svo_debug_level": (_i32, [_vp, _i32, _i32, _vp]),
     "rgbd_svo_debug_grid": (_i32, [_vp, _i32, _vp, _vp, _i32, _PI]),
     "rgbd_svo_retain_best": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _PI]),
+    "rgbd_create_adaptive": (_i32, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(AdaptiveParams), C.POINTER(Camera),
+                                    C.POINTER(_vp)]),
+    "rgbd_adaptive_get_thresholds": (_i32, [_vp, _vp]),
+    "rgbd_adaptive_set_thresholds": (_i32, [_vp, _vp]),
+    "rgbd_adaptive_rewind": (_i32, [_vp, _i32]),
+    "rgbd_adaptive_debug_cell": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_uint64), _PI, _PI, _vp, _i32, _PI]),
+    "rgbd_adaptive_keep_strongest": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "rgbd_destroy": (None, [_vp]),
     "rgbd_last_error": (C.c_char_p, [_vp]),
     "rgbd_max_keypoints": (_i32, [_vp]),
@@ -383,14 +408,22 @@ class Context:
     """One extractor + camera + device workspace (rgbd_create)."""
 
     def __init__(self, width=640, height=480, max_batch=1, orb: OrbParams | None = None,
-                 cam: Camera | None = None, device=0, svo: SvoParams | None = None):
-        """svo: an Extractor(SVO, BRIEF, NORMAL) context (rgbd_create_svo) instead of the ORBextractor."""
+                 cam: Camera | None = None, device=0, svo: SvoParams | None = None,
+                 adaptive: AdaptiveParams | None = None):
+        """svo: an Extractor(SVO, BRIEF, NORMAL) context (rgbd_create_svo) instead of the ORBextractor;
+        adaptive: an Extractor(FAST, BRIEF, ADAPTIVE) context (rgbd_create_adaptive)."""
+        if svo is not None and adaptive is not None:
+            raise ValueError("Context: svo and adaptive are different extractors; give one")
         self.orb = orb or orb_params()
         self.cam = cam or camera(535.4, 539.2, 320.1, 247.6)
         self.svo = svo
+        self.adaptive = adaptive
         self.W, self.H = width, height
         h = C.c_void_p()
-        if svo is not None:
+        if adaptive is not None:
+            st = lib().rgbd_create_adaptive(device, width, height, max_batch, C.byref(adaptive), C.byref(self.cam),
+                                            C.byref(h))
+        elif svo is not None:
             st = lib().rgbd_create_svo(device, width, height, max_batch, C.byref(svo), C.byref(self.cam), C.byref(h))
         else:
             st = lib().rgbd_create(device, width, height, max_batch, C.byref(self.orb), C.byref(self.cam), C.byref(h))
@@ -452,7 +485,46 @@ class Context:
         m = n.value
         return dict(kps=kps[:m].copy(), kps_un=kun[:m].copy(), desc=desc[:m].copy(), xyz=xyz[:m].copy())
 
-    # --- SVO + BRIEF (rgbd_create_svo contexts)
+    # --- adaptive FAST + BRIEF (rgbd_create_adaptive contexts)
+    @property
+    def adaptive_cells(self) -> int:
+        return self.adaptive.grid_rows * self.adaptive.grid_cols if self.adaptive is not None else 0
+
+    def adaptive_thresholds(self) -> np.ndarray:
+        """The cells' thresholds (f64, row-major) the next extraction starts from."""
+        out = np.zeros(max(self.adaptive_cells, 1), np.float64)
+        self._check(lib().rgbd_adaptive_get_thresholds(self._h, _ptr(out)), "adaptive_thresholds")
+        return out[:self.adaptive_cells].copy()
+
+    def set_adaptive_thresholds(self, thresh: np.ndarray):
+        thresh = np.ascontiguousarray(thresh, dtype=np.float64).reshape(-1)
+        if len(thresh) != self.adaptive_cells:
+            raise ValueError(f"set_adaptive_thresholds: {self.adaptive_cells} thresholds, one per cell")
+        self._check(lib().rgbd_adaptive_set_thresholds(self._h, _ptr(thresh)), "set_adaptive_thresholds")
+
+    def adaptive_rewind(self, k: int):
+        """The next extraction starts from the thresholds before frame last_B - k of the last batch (a copy on
+        the device, queued on the context's stream): for batches that overlap by k frames."""
+        self._check(lib().rgbd_adaptive_rewind(self._h, int(k)), "adaptive_rewind")
+
+    def adaptive_debug_cell(self, b: int, cell: int, cap=12288):
+        """(threshold before as f64, threshold used, tries, corners (x, y, score) of the last try in raster
+        order, ROI coordinates) of one cell of frame b of the last batch."""
+        bits, used, tries, n = C.c_uint64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        xys = np.zeros((cap, 3), np.int32)
+        self._check(lib().rgbd_adaptive_debug_cell(self._h, b, cell, C.byref(bits), C.byref(used), C.byref(tries),
+                                                   _ptr(xys), cap, C.byref(n)), "adaptive_debug_cell")
+        before = float(np.array([bits.value], np.uint64).view(np.float64)[0])
+        return before, used.value, tries.value, xys[:n.value].copy()
+
+    def adaptive_keep_strongest(self, resp: np.ndarray, N: int, depth_limit: int = -1) -> np.ndarray:
+        resp = np.ascontiguousarray(resp, dtype=np.float32)
+        order = np.zeros(max(len(resp), 1), np.int32)
+        self._check(lib().rgbd_adaptive_keep_strongest(self._h, _ptr(resp), len(resp), N, depth_limit, _ptr(order)),
+                    "adaptive_keep_strongest")
+        return order[:min(len(resp), N)].copy()
+
+    # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive contexts)
     def set_brief_pattern(self, pairs: np.ndarray):
         pairs = np.ascontiguousarray(pairs, dtype=np.int8).reshape(256, 4)
         self._check(lib().rgbd_svo_set_brief_pattern(self._h, _ptr(pairs)), "set_brief_pattern")

@@ -11,7 +11,7 @@
 #include "rgbd_internal.h"
 
 namespace rgbd {
-struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS;
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS;
 // the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
 struct OutSet {
     int* count = nullptr;
@@ -88,6 +88,7 @@ struct rgbd_ctx {
     rgbd::LaneWS* lanes = nullptr;       // device-resident RansacSE3 tracking chain (lanes_host.cpp)
     rgbd::CloudWS* cloud = nullptr;      // keyframe cloud (cloud_host.cpp)
     rgbd::SvoWS* svo = nullptr;          // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
+    rgbd::AdpWS* adaptive = nullptr;     // adaptive FAST + BRIEF extractor (adaptive_host.cpp); takes precedence over svo
     rgbd::ProjWS* proj = nullptr;        // projection-guided matching (project_host.cpp)
     rgbd::BaWS* pnpba = nullptr;         // motion-only bundle adjustment, PnPSolver (pnpba_host.cpp)
     rgbd::UmWS* umeyama = nullptr;       // Umeyama RANSAC, Ransac (umeyama_host.cpp)
@@ -151,4 +152,13 @@ void svo_free(rgbd_ctx* c);
 rgbd_status svo_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
                             const ExtractHook* after_fast);
 uint8_t* svo_gray_level(rgbd_ctx* c);   // level 0 of the SVO pyramid (frame 0): the gray upload target
+// adaptive_host.cpp: the Extractor(FAST, BRIEF, ADAPTIVE) front end of an rgbd_create_adaptive context
+rgbd_status adaptive_configure(rgbd_ctx* c, const rgbd_adaptive_params& p);   // validates; before the output allocations
+rgbd_status adaptive_alloc(rgbd_ctx* c);
+void adaptive_free(rgbd_ctx* c);
+rgbd_status adaptive_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                                 const ExtractHook* after_fast);
+uint8_t* adaptive_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
+rgbd_status adaptive_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
+rgbd_status adaptive_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
 }  // namespace rgbd

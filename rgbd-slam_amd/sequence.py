@@ -30,10 +30,15 @@ def batch_starts(n: int, B: int):
 
 
 def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1000, nnratio: float = 0.9,
-                   pose0=None, device: int = 0, max_frames: int | None = None, threads: int = 8, extras=None):
+                   pose0=None, device: int = 0, max_frames: int | None = None, threads: int = 8, extras=None,
+                   extractor: str = "orb"):
     """Poses Tcw [n, 4, 4] f32, per-frame status [n] (1: tracked / first frame) and inliers [n].  With
     solver "se3" and a dict `extras`, also the relative poses ('rel') and keyframe flags ('keyframe') of
-    Tracking's bookkeeping (for datasets.camera_trajectory_poses)."""
+    Tracking's bookkeeping (for datasets.camera_trajectory_poses).
+    extractor: "orb" (Extractor(ORB2, ORB2, NORMAL)), "svo" (SVO + BRIEF, the reference's default) or
+    "adaptive" (FAST + BRIEF, ADAPTIVE).  The adaptive extractor's per-cell thresholds are state: before every
+    later batch they are rewound on the device by the batches' overlap (1 frame with pnp, 2 with se3), so the
+    frames a batch repeats start from the thresholds they started from the first time."""
     import torch
     if B < 2 or (solver == "se3" and B < 3):
         raise ValueError(f"batch size must be at least 2 (pnp: batches overlap by one frame) or 3 (se3: by two), not {B}")
@@ -41,7 +46,15 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
     cam = ds.camera
     c = pkg.camera(cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["k1"], cam["k2"], cam["p1"], cam["p2"],
                    cam["k3"], cam["factor"])
-    ctx = pkg.Context(ds.W, ds.H, max_batch=B, orb=pkg.orb_params(nfeatures), cam=c, device=device)
+    if extractor == "orb":
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, orb=pkg.orb_params(nfeatures), cam=c, device=device)
+    elif extractor == "svo":
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, svo=pkg.svo_params(nfeatures))
+    elif extractor == "adaptive":
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, adaptive=pkg.adaptive_params(nfeatures))
+    else:
+        raise ValueError(f"extractor must be 'orb', 'svo' or 'adaptive', not {extractor!r}")
+    adaptive = extractor == "adaptive"
     dev = torch.device("cuda", device)
     poses = np.zeros((n, 4, 4), np.float32)
     status = np.zeros(n, np.int32)
@@ -66,6 +79,8 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
             for k, s in enumerate(starts):
                 while nxt < len(starts) and len(inflight) < 3:
                     fr = upload(starts[nxt])
+                    if adaptive and nxt > 0:
+                        ctx.adaptive_rewind(1)
                     ctx.pnp_track_submit(fr[0].data_ptr(), fr[1].data_ptr(), fr[2], nnratio, prm)
                     inflight.append((starts[nxt], fr))
                     nxt += 1
@@ -87,6 +102,8 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
             while True:
                 fr = upload(s)
                 k0 = 2 if state.valid else 1
+                if adaptive and s > 0:
+                    ctx.adaptive_rewind(2)
                 pb, sb, ib, rb, kb = ctx.track_batch_kf(fr[0].data_ptr(), fr[1].data_ptr(), fr[2], nnratio, prm, rng,
                                                         sticky, state, poses[s + k0 - 1])
                 if k0 == 1:

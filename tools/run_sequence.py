@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--solver", choices=["pnp", "se3"], default="pnp")
     ap.add_argument("--nfeatures", type=int, default=1000)
+    ap.add_argument("--extractor", choices=["orb", "svo", "adaptive"], default="orb",
+                    help="ORB2 (default), SVO + BRIEF, or the adaptive FAST + BRIEF extractor")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--out", default="CameraTrajectory.txt")
     ap.add_argument("--posegraph", action="store_true",
@@ -40,7 +42,7 @@ def main():
     t0 = time.perf_counter()
     extras = {}
     poses, status, ninl = track_sequence(pkg, ds, B=args.batch, solver=args.solver, nfeatures=args.nfeatures,
-                                         max_frames=args.max_frames, extras=extras)
+                                         max_frames=args.max_frames, extras=extras, extractor=args.extractor)
     dt = time.perf_counter() - t0
     n = len(poses)
     if args.posegraph:
