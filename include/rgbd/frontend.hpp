@@ -93,9 +93,9 @@ public:
 };
 
 // Extractor(eType detector, eType descriptor, eMode mode) -- Features/Extractor.cpp:15-22.  The accelerated
-// pairs are (ORB2, ORB2) and (SVO, BRIEF) in NORMAL mode (main.cpp:31 runs the latter) and (FAST, BRIEF) in
-// ADAPTIVE mode (createAdaptiveDetector, :82-109); the OpenCV stock detectors / descriptors and the other
-// ADAPTIVE adjusters (GFTT, ORB, SURF, SIFT) are not on this path and throw.
+// pairs are (ORB2, ORB2), (SVO, BRIEF) (main.cpp:31 runs the latter) and (GFTT, BRIEF) (cv::GFTTDetector, :178-181)
+// in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode (createAdaptiveDetector, :82-109); the other OpenCV stock
+// detectors / descriptors and the other ADAPTIVE adjusters (GFTT, ORB, SURF, SIFT) are not on this path and throw.
 class Extractor : public ExtractorBase {
 public:
     enum eType { ORB = 0, ORB2, SVO, FAST, GFTT, STAR, BRISK, FREAK, BRIEF, LATCH, SURF, SIFT };
@@ -108,8 +108,9 @@ public:
     {
         const bool orb2 = detector == ORB2 && descriptor == ORB2, svo = detector == SVO && descriptor == BRIEF;
         const bool adaptive = mode == ADAPTIVE && detector == FAST && descriptor == BRIEF;
-        if (!adaptive && (mode != NORMAL || !(orb2 || svo)))
-            throw Error("Extractor: only (ORB2, ORB2) and (SVO, BRIEF) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
+        const bool gftt = detector == GFTT && descriptor == BRIEF;
+        if (!adaptive && (mode != NORMAL || !(orb2 || svo || gftt)))
+            throw Error("Extractor: only (ORB2, ORB2), (SVO, BRIEF) and (GFTT, BRIEF) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
         cam_ = cam;
         setParameters(1000, 1.2f, 8, 20, 7);   // :21
     }
@@ -127,6 +128,10 @@ public:
             // init()'s tables, which the getters below report
             rgbd_adaptive_params p{nfeatures, 600, 3, 3, 31, 5, 0, 0, 20.0, 2.0, 10000.0, 1.3, 0.7};
             s = rgbd_create_adaptive(device_, W_, H_, maxB_, &p, &cam_, &c);
+        } else if (mDetectorType == GFTT) {
+            // GFTTDetector::create(nfeatures, 0.01, 3, 3, false, 0.04), :178-181: nfeatures is maxCorners
+            rgbd_gftt_params p{nfeatures, 0, 0.01, 3.0};
+            s = rgbd_create_gftt(device_, W_, H_, maxB_, &p, &cam_, &c);
         } else if (mDetectorType == SVO) {
             rgbd_svo_params p{nfeatures, nlevels, 5, 20, 0};   // SVOextractor(nlevels, 5, 20), :162-165
             s = rgbd_create_svo(device_, W_, H_, maxB_, &p, &cam_, &c);
@@ -136,7 +141,7 @@ public:
         }
         adopt(c, s, cam_, "Extractor");
     }
-    // getters (:97-151); the SVO and ADAPTIVE branches report init()'s tables, the ORB2 branch ORBextractor's
+    // getters (:97-151); the SVO, GFTT and ADAPTIVE branches report init()'s tables, the ORB2 branch ORBextractor's
     // (same values)
     int getLevels() const { return nlevels_; }
     float getScaleFactor() const { return scale_; }
@@ -164,7 +169,7 @@ public:
         for (float& v : f) v = 1.0f / v;
         return f;
     }
-    // OpenCV's own BRIEF tests (opencv_contrib generated_32.i), 256 x {y1, x1, y2, x2}; SVO and ADAPTIVE contexts only
+    // OpenCV's own BRIEF tests (opencv_contrib generated_32.i), 256 x {y1, x1, y2, x2}; SVO, GFTT and ADAPTIVE contexts only
     void setBriefPattern(const int8_t* pairs) { check(ctx_.get(), rgbd_svo_set_brief_pattern(ctx_.get(), pairs), "setBriefPattern"); }
 
     eType mDetectorType, mDescriptorType;

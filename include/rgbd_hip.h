@@ -226,6 +226,44 @@ rgbd_status rgbd_adaptive_debug_cell(rgbd_ctx* ctx, int32_t b, int32_t cell, uin
 rgbd_status rgbd_adaptive_keep_strongest(rgbd_ctx* ctx, const float* resp, int32_t n, int32_t N, int32_t depth_limit,
                                          int32_t* order);
 
+/* ------------------------------------------------------------------ Shi-Tomasi GFTT + BRIEF extractor */
+/* Extractor(GFTT, BRIEF, NORMAL) (Features/Extractor.cpp:50-61, 178-181): cv::GFTTDetector::create(nfeatures,
+ * 0.01, 3, 3, false, 0.04), retainBest (never fires: at most nfeatures corners) and
+ * cv::xfeatures2d::BriefDescriptorExtractor (32 bytes).  OpenCV 3.x's goodFeaturesToTrack restated: the minimum
+ * eigenvalue e of the 3x3-summed Sobel covariance (f32, box sums in f64), thr = (float)(max e * quality_level),
+ * candidates = interior pixels with e > thr that equal their thresholded 3x3 maximum, ranked by descending e
+ * (equal values: the higher raster index first), then the sequential greedy that accepts a candidate unless an
+ * accepted corner lies at integer dx*dx + dy*dy < min_distance^2, up to nfeatures.  Keypoints: size 3, angle -1,
+ * response 0, octave 0, in acceptance order.  DESIGN.md, "GFTT + BRIEF definition"; tests/gftt_model.py.
+ * The extractor has no frame-to-frame state.
+ * Shapes: the refusals of a one-level ORB geometry (as for rgbd_create_adaptive), sides of 2..2047 px, and
+ * RGBD_ERR_UNSUPPORTED before any allocation unless 1 <= nfeatures <= 12288, 0 < quality_level < 1,
+ * min_distance finite in [0, 64] and 0 <= cand_cap <= 1048576. */
+typedef struct {
+    int32_t nfeatures;        /* 1000: maxCorners (Extractor::setParameters) */
+    int32_t cand_cap;         /* stored candidates per frame; 0: 32768 (a uniform-noise 640 x 480 frame has about
+                                 20,300).  A frame with more fails alone with RGBD_ERR_CAPACITY */
+    double quality_level;     /* 0.01 */
+    double min_distance;      /* 3; below 1 there is no spacing test */
+} rgbd_gftt_params;
+rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, const rgbd_gftt_params* params,
+                             const rgbd_camera* cam, rgbd_ctx** out);
+/* The raw map e (width * height floats) of frame b of the last batch, recomputed from its gray image. */
+rgbd_status rgbd_gftt_debug_eig(rgbd_ctx* ctx, int32_t b, float* out);
+/* Frame b of the last batch: the bits of M = max e, the number of candidates found (it may exceed cand_cap),
+ * and the accepted corners in acceptance order, before BRIEF's border filter, as (x, y) pairs with their
+ * eigenvalues.  xy / val may be null to read the counts only. */
+rgbd_status rgbd_gftt_debug_corners(rgbd_ctx* ctx, int32_t b, uint32_t* max_bits, int32_t* n_candidates, int32_t* xy,
+                                    float* val, int32_t cap, int32_t* n);
+/* How many ranks the greedy consumed on frame b of the last batch (all of them when the list ran out). */
+rgbd_status rgbd_gftt_debug_ranks(rgbd_ctx* ctx, int32_t b, int32_t* ranks);
+/* The device's rank + spacing stage (k_gftt_select, the code the extraction runs) on a host list of n distinct
+ * points (x, y) inside W x H (sides <= 2047) with positive finite values: out_idx[0..m) = the accepted points'
+ * list indices in acceptance order (room for min(n, max_corners)).  chunk = ranks per pass (1..4096; 0: the
+ * default for max_corners); max_corners in 1..12288; n <= 1048576. */
+rgbd_status rgbd_gftt_select(rgbd_ctx* ctx, const int32_t* xy, const float* val, int32_t n, int32_t W, int32_t H,
+                             double min_distance, int32_t max_corners, int32_t chunk, int32_t* out_idx, int32_t* m);
+
 /* ------------------------------------------------------------------ matching */
 /* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}.
  * At most 65536 train rows (nt): the kernel's rank key holds the train index in 16 bits.  A larger nt

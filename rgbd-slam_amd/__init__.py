@@ -85,6 +85,18 @@ def adaptive_params(nfeatures=1000, min_features=600, grid_rows=3, grid_cols=3, 
                           init_thresh, min_thresh, max_thresh, increase, decrease)
 
 
+class GfttParams(C.Structure):
+    """rgbd_gftt_params: Extractor(GFTT, BRIEF, NORMAL) (Features/Extractor.cpp:178-181)."""
+    _fields_ = [("nfeatures", C.c_int32), ("cand_cap", C.c_int32), ("quality_level", C.c_double),
+                ("min_distance", C.c_double)]
+
+
+def gftt_params(nfeatures=1000, quality_level=0.01, min_distance=3.0, cand_cap=0) -> GfttParams:
+    """The reference's values: GFTTDetector::create(nfeatures, 0.01, 3, ...); cand_cap 0 = 32768 stored
+    candidates per frame (a frame with more raises RGBD_ERR_CAPACITY for that frame alone)."""
+    return GfttParams(nfeatures, cand_cap, quality_level, min_distance)
+
+
 class CloudParams(C.Structure):
     _fields_ = [("stride", C.c_int32), ("zmin", C.c_float), ("zmax", C.c_float), ("leaf", C.c_float),
                 ("sor_k", C.c_int32), ("sor_std", C.c_double)]
@@ -185,6 +197,12 @@ _SIGS = {
     "rgbd_adaptive_rewind": (_i32, [_vp, _i32]),
     "rgbd_adaptive_debug_cell": (_i32, [_vp, _i32, _i32, C.POINTER(C.c_uint64), _PI, _PI, _vp, _i32, _PI]),
     "rgbd_adaptive_keep_strongest": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "rgbd_create_gftt": (_i32, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(GfttParams), C.POINTER(Camera),
+                                C.POINTER(_vp)]),
+    "rgbd_gftt_debug_eig": (_i32, [_vp, _i32, _vp]),
+    "rgbd_gftt_debug_corners": (_i32, [_vp, _i32, C.POINTER(C.c_uint32), _PI, _vp, _vp, _i32, _PI]),
+    "rgbd_gftt_debug_ranks": (_i32, [_vp, _i32, _PI]),
+    "rgbd_gftt_select": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _i32, _i32, _vp, _PI]),
     "rgbd_destroy": (None, [_vp]),
     "rgbd_last_error": (C.c_char_p, [_vp]),
     "rgbd_max_keypoints": (_i32, [_vp]),
@@ -409,18 +427,22 @@ class Context:
 
     def __init__(self, width=640, height=480, max_batch=1, orb: OrbParams | None = None,
                  cam: Camera | None = None, device=0, svo: SvoParams | None = None,
-                 adaptive: AdaptiveParams | None = None):
+                 adaptive: AdaptiveParams | None = None, gftt: GfttParams | None = None):
         """svo: an Extractor(SVO, BRIEF, NORMAL) context (rgbd_create_svo) instead of the ORBextractor;
-        adaptive: an Extractor(FAST, BRIEF, ADAPTIVE) context (rgbd_create_adaptive)."""
-        if svo is not None and adaptive is not None:
-            raise ValueError("Context: svo and adaptive are different extractors; give one")
+        adaptive: an Extractor(FAST, BRIEF, ADAPTIVE) context (rgbd_create_adaptive);
+        gftt: an Extractor(GFTT, BRIEF, NORMAL) context (rgbd_create_gftt)."""
+        if (svo is not None) + (adaptive is not None) + (gftt is not None) > 1:
+            raise ValueError("Context: svo, adaptive and gftt are different extractors; give one")
         self.orb = orb or orb_params()
         self.cam = cam or camera(535.4, 539.2, 320.1, 247.6)
         self.svo = svo
         self.adaptive = adaptive
+        self.gftt = gftt
         self.W, self.H = width, height
         h = C.c_void_p()
-        if adaptive is not None:
+        if gftt is not None:
+            st = lib().rgbd_create_gftt(device, width, height, max_batch, C.byref(gftt), C.byref(self.cam), C.byref(h))
+        elif adaptive is not None:
             st = lib().rgbd_create_adaptive(device, width, height, max_batch, C.byref(adaptive), C.byref(self.cam),
                                             C.byref(h))
         elif svo is not None:
@@ -524,7 +546,41 @@ class Context:
                     "adaptive_keep_strongest")
         return order[:min(len(resp), N)].copy()
 
-    # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive contexts)
+    # --- Shi-Tomasi GFTT + BRIEF (rgbd_create_gftt contexts)
+    def gftt_debug_eig(self, b: int) -> np.ndarray:
+        """The raw minimum-eigenvalue map e [H, W] f32 of frame b of the last batch."""
+        out = np.zeros((self.H, self.W), np.float32)
+        self._check(lib().rgbd_gftt_debug_eig(self._h, b, _ptr(out)), "gftt_debug_eig")
+        return out
+
+    def gftt_debug_corners(self, b: int):
+        """Frame b of the last batch: dict(M = max e (f32), n_candidates, corners [m, 2] int32 (x, y) in
+        acceptance order before BRIEF's border filter, vals [m] f32, ranks = ranks the greedy consumed)."""
+        cap = self.gftt.nfeatures if self.gftt is not None else 1
+        bits, nc, n, rk = C.c_uint32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        xy = np.zeros((cap, 2), np.int32)
+        val = np.zeros(cap, np.float32)
+        self._check(lib().rgbd_gftt_debug_corners(self._h, b, C.byref(bits), C.byref(nc), _ptr(xy), _ptr(val), cap,
+                                                  C.byref(n)), "gftt_debug_corners")
+        self._check(lib().rgbd_gftt_debug_ranks(self._h, b, C.byref(rk)), "gftt_debug_ranks")
+        M = np.array([bits.value], np.uint32).view(np.float32)[0]
+        return dict(M=M, n_candidates=nc.value, corners=xy[:n.value].copy(), vals=val[:n.value].copy(), ranks=rk.value)
+
+    def gftt_select(self, xy: np.ndarray, val: np.ndarray, W: int, H: int, min_distance: float, max_corners: int,
+                    chunk: int = 0) -> np.ndarray:
+        """The device's rank + spacing stage on a host list of distinct points: the accepted points' indices in
+        acceptance order.  chunk = ranks per pass (0: the default for max_corners)."""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        val = np.ascontiguousarray(val, dtype=np.float32).reshape(-1)
+        if len(xy) != len(val):
+            raise ValueError("gftt_select: one value per point")
+        out = np.zeros(max(min(len(xy), max_corners), 1), np.int32)
+        m = C.c_int32(0)
+        self._check(lib().rgbd_gftt_select(self._h, _ptr(xy), _ptr(val), len(xy), W, H, float(min_distance), max_corners,
+                                           chunk, _ptr(out), C.byref(m)), "gftt_select")
+        return out[:m.value].copy()
+
+    # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive and GFTT contexts)
     def set_brief_pattern(self, pairs: np.ndarray):
         pairs = np.ascontiguousarray(pairs, dtype=np.int8).reshape(256, 4)
         self._check(lib().rgbd_svo_set_brief_pattern(self._h, _ptr(pairs)), "set_brief_pattern")

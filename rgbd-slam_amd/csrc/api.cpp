@@ -105,11 +105,15 @@ static rgbd_status mark_extracted(rgbd_ctx* c)
 rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
                         const rgbd::ExtractHook* after_fast = nullptr)
 {
-    // per-frame capacity flags (k_distribute / k_svo_select / k_adp_select), cleared for every extraction
+    // per-frame capacity flags (k_distribute / k_svo_select / k_adp_select / k_gftt_cand), cleared for every extraction
     rgbd_status s0 = check_hip(c, hipMemsetAsync(c->d_err, 0, sizeof(int) * (size_t)B, c->stream), "clear err");
     if (s0) return s0;
     if (c->adaptive) {
         if ((s0 = adaptive_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
+        return mark_extracted(c);
+    }
+    if (c->gftt) {
+        if ((s0 = gftt_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
         return mark_extracted(c);
     }
     if (c->svo) {
@@ -192,9 +196,7 @@ rgbd_status read_frame(rgbd_ctx* c, int b, rgbd_keypoint* kps, rgbd_keypoint* ku
     if ((s = check_hip(c, hipMemcpyAsync(&errflag, c->d_err + b, sizeof(int), hipMemcpyDeviceToHost, c->stream), "read err")))
         return s;
     if ((s = check_hip(c, hipStreamSynchronize(c->stream), "sync"))) return s;
-    if (errflag & 4) return fail(c, RGBD_ERR_CAPACITY, "adaptive: a cell has more corners at its threshold than cell_cap stores");
-    if (errflag & 2) return fail(c, RGBD_ERR_CAPACITY, "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints");
-    if (errflag) return fail(c, RGBD_ERR_CAPACITY, "quadtree node capacity exceeded");
+    if (errflag) return fail(c, RGBD_ERR_CAPACITY, extract_flag_message(errflag));
     if (n) *n = cnt;
     if (cnt > cap) return fail(c, RGBD_ERR_CAPACITY, "output capacity smaller than keypoint count");
     if (cnt == 0) return RGBD_OK;
@@ -217,7 +219,8 @@ rgbd_status upload_table(rgbd_ctx* c, DevBuf<D>& d, const std::vector<T>& v, con
 }
 
 rgbd_status create_ctx(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
-                       const rgbd_svo_params* svo, const rgbd_adaptive_params* adp, const rgbd_camera* cam, rgbd_ctx** out)
+                       const rgbd_svo_params* svo, const rgbd_adaptive_params* adp, const rgbd_gftt_params* gftt,
+                       const rgbd_camera* cam, rgbd_ctx** out)
 {
     if (!out || !orb || !cam || max_batch < 1) return RGBD_ERR_ARG;
     rgbd_ctx* c = new rgbd_ctx();
@@ -235,6 +238,10 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (adp) {
         const rgbd_status sa = adaptive_configure(c, *adp);   // sets cfg.kp_cap before the allocations
         if (sa) return sa;
+    }
+    if (gftt) {
+        const rgbd_status sg = gftt_configure(c, *gftt);   // likewise
+        if (sg) return sg;
     }
     if (s) return s;
     if (svo && (s = svo_configure(c, *svo))) return s;   // sets cfg.kp_cap before the allocations
@@ -288,6 +295,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (!s) s = check_hip(c, hipMemset(c->d_blur, 0, B * C.frame_pyr_bytes + 64), "memset blur");
     if (!s && svo) s = svo_alloc(c);
     if (!s && adp) s = adaptive_alloc(c);
+    if (!s && gftt) s = gftt_alloc(c);
     return s;
 }
 
@@ -298,7 +306,7 @@ extern "C" {
 rgbd_status rgbd_create(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
                         const rgbd_camera* cam, rgbd_ctx** out)
 {
-    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, const rgbd_svo_params* svo,
@@ -309,7 +317,7 @@ rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, co
     // fields only shape the scale tables the reference's getters report (the ORB workspace is never run,
     // so its budget is kept small)
     const rgbd_orb_params orb{std::max(1, std::min(svo->nfeatures, 1000)), 1.2f, 8, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batch, const rgbd_adaptive_params* params,
@@ -319,7 +327,16 @@ rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batc
     // the ORB workspace is never run: a one-level ORB geometry (every adaptive keypoint has octave 0), so of the
     // ORB shape refusals only level 0's remain (the 8-level geometry refuses e.g. 320 x 256 for its level 7)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, nullptr, cam, out);
+}
+
+rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, const rgbd_gftt_params* params,
+                             const rgbd_camera* cam, rgbd_ctx** out)
+{
+    if (!params) return RGBD_ERR_ARG;
+    // as for rgbd_create_adaptive: a one-level ORB geometry that is never run (every GFTT keypoint has octave 0)
+    const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, params, cam, out);
 }
 
 void rgbd_destroy(rgbd_ctx* c)
@@ -339,6 +356,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::bow_free(c);
     rgbd::svo_free(c);
     rgbd::adaptive_free(c);
+    rgbd::gftt_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     const hipStream_t own = c->own_stream, solve = c->solve_stream, match = c->match_stream;
@@ -396,6 +414,9 @@ rgbd_status rgbd_detect_and_compute(rgbd_ctx* c, const uint8_t* gray, int32_t st
     if (s) return s;
     if (c->adaptive)
         s = check_hip(c, hipMemcpy2DAsync(adaptive_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
+                      "upload gray");
+    else if (c->gftt)
+        s = check_hip(c, hipMemcpy2DAsync(gftt_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
                       "upload gray");
     else if (c->svo)
         s = check_hip(c, hipMemcpy2DAsync(svo_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),

@@ -11,7 +11,7 @@
 #include "rgbd_internal.h"
 
 namespace rgbd {
-struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS;
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS; struct GfttWS;
 // the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
 struct OutSet {
     int* count = nullptr;
@@ -89,6 +89,7 @@ struct rgbd_ctx {
     rgbd::CloudWS* cloud = nullptr;      // keyframe cloud (cloud_host.cpp)
     rgbd::SvoWS* svo = nullptr;          // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
     rgbd::AdpWS* adaptive = nullptr;     // adaptive FAST + BRIEF extractor (adaptive_host.cpp); takes precedence over svo
+    rgbd::GfttWS* gftt = nullptr;        // Shi-Tomasi GFTT + BRIEF extractor (gftt_host.cpp); a context has at most one of svo / adaptive / gftt
     rgbd::ProjWS* proj = nullptr;        // projection-guided matching (project_host.cpp)
     rgbd::BaWS* pnpba = nullptr;         // motion-only bundle adjustment, PnPSolver (pnpba_host.cpp)
     rgbd::UmWS* umeyama = nullptr;       // Umeyama RANSAC, Ransac (umeyama_host.cpp)
@@ -117,6 +118,14 @@ int timer_begin(rgbd_ctx* c, const char* name, hipStream_t st = nullptr);   // n
 void timer_end(rgbd_ctx* c, int tok);
 void timer_flush(rgbd_ctx* c);
 rgbd_status fail(rgbd_ctx* c, rgbd_status code, const std::string& msg);
+// what a frame's extraction flag (rgbd_ctx::d_err, nonzero) says, for RGBD_ERR_CAPACITY: one wording on every path
+inline const char* extract_flag_message(int flag)
+{
+    if (flag & 8) return "gftt: the frame has more candidates than cand_cap stores";
+    if (flag & 4) return "adaptive: a cell has more corners at its threshold than cell_cap stores";
+    if (flag & 2) return "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints";
+    return "quadtree node capacity exceeded";
+}
 rgbd_status check_hip(rgbd_ctx* c, hipError_t e, const char* what);
 // cv::Mat(CV_32F) * cv::Mat on 4x4 row-major matrices: OpenCV's gemm for 32F accumulates each dot product in
 // double in k order (GEMMSingleMul<float,double>) and rounds once
@@ -161,4 +170,13 @@ rgbd_status adaptive_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16
 uint8_t* adaptive_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
 rgbd_status adaptive_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
 rgbd_status adaptive_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
+// gftt_host.cpp: the Extractor(GFTT, BRIEF, NORMAL) front end of an rgbd_create_gftt context
+rgbd_status gftt_configure(rgbd_ctx* c, const rgbd_gftt_params& p);   // validates; before the output allocations
+rgbd_status gftt_alloc(rgbd_ctx* c);
+void gftt_free(rgbd_ctx* c);
+rgbd_status gftt_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                             const ExtractHook* after_fast);
+uint8_t* gftt_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
+rgbd_status gftt_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
+rgbd_status gftt_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
 }  // namespace rgbd

@@ -670,9 +670,7 @@ static rgbd_status track_collect(rgbd_ctx* c, PnpWS* w, int B, float nnratio, co
         s = pnp_finish(c, w, P, cam, prm, res.data());
     if (s) return s;
     for (int b = 0; b < B; b++)   // the extraction's per-frame flags (copied before the solve's events)
-        if (w->h_err[b]) return fail(c, RGBD_ERR_CAPACITY, (w->h_err[b] & 2)
-                                     ? "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints"
-                                     : "quadtree node capacity exceeded");
+        if (w->h_err[b]) return fail(c, RGBD_ERR_CAPACITY, extract_flag_message(w->h_err[b]));
     for (int b = 1; b < B; b++) {
         const PnpResult& r = res[b - 1];
         if (r.ok) {

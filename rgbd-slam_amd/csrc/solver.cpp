@@ -371,8 +371,7 @@ static rgbd_status track_chain(rgbd_ctx* c, const void* d_bgr, const void* d_dep
                     (ts && B >= 2) ? ts->flags2 : nullptr, (ts && B >= 2) ? ts->flags1 : nullptr);
     if (s) return s;
     for (int b = 0; b < B; b++)
-        if (errf[b]) return fail(c, RGBD_ERR_CAPACITY, (errf[b] & 2) ? "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints"
-                                                                    : "quadtree node capacity exceeded");
+        if (errf[b]) return fail(c, RGBD_ERR_CAPACITY, extract_flag_message(errf[b]));
     status[0] = 1;
     if (n_inliers) n_inliers[0] = 0;
     // Tracking's bookkeeping (ts != NULL; System/Tracking.cpp:39-73, 227-256): P = every frame's current
@@ -467,8 +466,7 @@ rgbd_status rgbd_track_lanes(rgbd_ctx* c, const void* d_bgr, const void* d_depth
     if ((s = lanes_track(c, B, nnratio, *prm, sp.data(), L, rngs, stickies, nullptr, nullptr, po, nullptr, nullptr)))
         return s;
     for (int b = 0; b < B; b++)
-        if (errf[b]) return fail(c, RGBD_ERR_CAPACITY, (errf[b] & 2) ? "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints"
-                                                                    : "quadtree node capacity exceeded");
+        if (errf[b]) return fail(c, RGBD_ERR_CAPACITY, extract_flag_message(errf[b]));
     for (int l = 0; l < L; l++) {   // lane-major rows: frame f of lane l at row f + l
         const int r0 = sp[l].start + l;
         status[r0] = 1;

@@ -169,12 +169,14 @@ extern "C" {
 rgbd_status rgbd_svo_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs)
 {
     if (!c || !pairs) return RGBD_ERR_ARG;
-    if (!c->svo && !c->adaptive) return fail(c, RGBD_ERR_ARG, "not an SVO or adaptive context (rgbd_create_svo, rgbd_create_adaptive)");
+    if (!c->svo && !c->adaptive && !c->gftt)
+        return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive or GFTT context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt)");
     for (int i = 0; i < 1024; i++)
         if (pairs[i] < -24 || pairs[i] > 24) return fail(c, RGBD_ERR_ARG, "BRIEF offsets must lie in [-24, 24]");
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
     if (c->adaptive) return adaptive_set_brief_pattern(c, pairs);
+    if (c->gftt) return gftt_set_brief_pattern(c, pairs);
     std::memcpy(ws(c)->pattern, pairs, 1024);
     if ((s = upload_pattern(c, ws(c)))) return s;
     return check_hip(c, hipStreamSynchronize(c->stream), "sync");
@@ -184,7 +186,9 @@ rgbd_status rgbd_svo_get_brief_pattern(rgbd_ctx* c, int8_t* pairs)
 {
     if (!c || !pairs) return RGBD_ERR_ARG;
     if (c->adaptive) return adaptive_get_brief_pattern(c, pairs);
-    if (!c->svo) return fail(c, RGBD_ERR_ARG, "not an SVO or adaptive context (rgbd_create_svo, rgbd_create_adaptive)");
+    if (c->gftt) return gftt_get_brief_pattern(c, pairs);
+    if (!c->svo)
+        return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive or GFTT context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt)");
     std::memcpy(pairs, ws(c)->pattern, 1024);
     return RGBD_OK;
 }

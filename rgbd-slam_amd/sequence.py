@@ -35,9 +35,12 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
     """Poses Tcw [n, 4, 4] f32, per-frame status [n] (1: tracked / first frame) and inliers [n].  With
     solver "se3" and a dict `extras`, also the relative poses ('rel') and keyframe flags ('keyframe') of
     Tracking's bookkeeping (for datasets.camera_trajectory_poses).
-    extractor: "orb" (Extractor(ORB2, ORB2, NORMAL)), "svo" (SVO + BRIEF, the reference's default) or
-    "adaptive" (FAST + BRIEF, ADAPTIVE).  The adaptive extractor's per-cell thresholds are state: before every
-    later batch they are rewound on the device by the batches' overlap (1 frame with pnp, 2 with se3), so the
+    extractor:
+      - "orb": Extractor(ORB2, ORB2, NORMAL);
+      - "svo": SVO + BRIEF, the reference's default;
+      - "adaptive": FAST + BRIEF, ADAPTIVE;
+      - "gftt": Shi-Tomasi GFTT + BRIEF, NORMAL (no state between frames).
+    The adaptive extractor's per-cell thresholds are state: before every later batch they are rewound on the device by the batches' overlap (1 frame with pnp, 2 with se3), so the
     frames a batch repeats start from the thresholds they started from the first time."""
     import torch
     if B < 2 or (solver == "se3" and B < 3):
@@ -52,8 +55,10 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
         ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, svo=pkg.svo_params(nfeatures))
     elif extractor == "adaptive":
         ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, adaptive=pkg.adaptive_params(nfeatures))
+    elif extractor == "gftt":
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, gftt=pkg.gftt_params(nfeatures))
     else:
-        raise ValueError(f"extractor must be 'orb', 'svo' or 'adaptive', not {extractor!r}")
+        raise ValueError(f"extractor must be 'orb', 'svo', 'adaptive' or 'gftt', not {extractor!r}")
     adaptive = extractor == "adaptive"
     dev = torch.device("cuda", device)
     poses = np.zeros((n, 4, 4), np.float32)
