@@ -93,8 +93,8 @@ public:
 };
 
 // Extractor(eType detector, eType descriptor, eMode mode) -- Features/Extractor.cpp:15-22.  The accelerated
-// pairs are (ORB2, ORB2), (SVO, BRIEF) (main.cpp:31 runs the latter) and (GFTT, BRIEF) (cv::GFTTDetector, :178-181)
-// in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode (createAdaptiveDetector, :82-109); the other OpenCV stock
+// pairs are (ORB2, ORB2), (SVO, BRIEF) (main.cpp:31 runs the latter), (GFTT, BRIEF) (cv::GFTTDetector, :178-181) and
+// (ORB, ORB) (cv::ORB as detector and descriptor, :163-166, 216-218) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode (createAdaptiveDetector, :82-109); the other OpenCV stock
 // detectors / descriptors and the other ADAPTIVE adjusters (GFTT, ORB, SURF, SIFT) are not on this path and throw.
 class Extractor : public ExtractorBase {
 public:
@@ -109,8 +109,9 @@ public:
         const bool orb2 = detector == ORB2 && descriptor == ORB2, svo = detector == SVO && descriptor == BRIEF;
         const bool adaptive = mode == ADAPTIVE && detector == FAST && descriptor == BRIEF;
         const bool gftt = detector == GFTT && descriptor == BRIEF;
-        if (!adaptive && (mode != NORMAL || !(orb2 || svo || gftt)))
-            throw Error("Extractor: only (ORB2, ORB2), (SVO, BRIEF) and (GFTT, BRIEF) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
+        const bool cvorb = detector == ORB && descriptor == ORB;
+        if (!adaptive && (mode != NORMAL || !(orb2 || svo || gftt || cvorb)))
+            throw Error("Extractor: only (ORB2, ORB2), (SVO, BRIEF), (GFTT, BRIEF) and (ORB, ORB) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
         cam_ = cam;
         setParameters(1000, 1.2f, 8, 20, 7);   // :21
     }
@@ -132,6 +133,11 @@ public:
             // GFTTDetector::create(nfeatures, 0.01, 3, 3, false, 0.04), :178-181: nfeatures is maxCorners
             rgbd_gftt_params p{nfeatures, 0, 0.01, 3.0};
             s = rgbd_create_gftt(device_, W_, H_, maxB_, &p, &cam_, &c);
+        } else if (mDetectorType == ORB) {
+            // cv::ORB::create(nfeatures, scaleFactor, nlevels), :163-166: edgeThreshold 31, fastThreshold 20; the
+            // corner lists at their largest (12288 per level), the default output slack
+            rgbd_cvorb_params p{nfeatures, scaleFactor, nlevels, 31, 20, 12288, 0};
+            s = rgbd_create_cvorb(device_, W_, H_, maxB_, &p, &cam_, &c);
         } else if (mDetectorType == SVO) {
             rgbd_svo_params p{nfeatures, nlevels, 5, 20, 0};   // SVOextractor(nlevels, 5, 20), :162-165
             s = rgbd_create_svo(device_, W_, H_, maxB_, &p, &cam_, &c);
@@ -141,7 +147,7 @@ public:
         }
         adopt(c, s, cam_, "Extractor");
     }
-    // getters (:97-151); the SVO, GFTT and ADAPTIVE branches report init()'s tables, the ORB2 branch ORBextractor's
+    // getters (:97-151); the SVO, GFTT, ORB and ADAPTIVE branches report init()'s tables, the ORB2 branch ORBextractor's
     // (same values)
     int getLevels() const { return nlevels_; }
     float getScaleFactor() const { return scale_; }

@@ -264,6 +264,44 @@ rgbd_status rgbd_gftt_debug_ranks(rgbd_ctx* ctx, int32_t b, int32_t* ranks);
 rgbd_status rgbd_gftt_select(rgbd_ctx* ctx, const int32_t* xy, const float* val, int32_t n, int32_t W, int32_t H,
                              double min_distance, int32_t max_corners, int32_t chunk, int32_t* out_idx, int32_t* m);
 
+/* ------------------------------------------------------------------ OpenCV ORB extractor */
+/* Extractor(ORB, ORB, NORMAL) (Features/Extractor.cpp:50-61, 163-166, 216-218): cv::ORB::create(nfeatures,
+ * scaleFactor, nlevels) as detector, retainBest(nfeatures), cv::ORB::create() as descriptor.  OpenCV 3.4's orb.cpp
+ * restated: per pyramid level cv::FAST(fast_threshold, nonmax) over the whole level, runByImageBorder(
+ * edge_threshold), retainBest(2 N_l) on the FAST score, the Harris response (7 x 7 block, k = 0.04), retainBest(N_l)
+ * on it, IC_Angle, pt *= layerScale; then the frame-level retainBest and compute()'s provided-keypoints path
+ * (runByImageBorder(31) at image scale, regrouping by octave, 7x7 sigma-2 blur, the 256 steered tests of
+ * bit_pattern_31_).  Keypoints: size 31 * layerScale, response = Harris, class_id -1, level-major.  Fixed:
+ * firstLevel 0, WTA_K 2, HARRIS_SCORE, patchSize 31, no mask.  DESIGN.md, "OpenCV ORB definition";
+ * tests/cvorb_model.py.  No frame-to-frame state.  The pyramid and the blur are the ORB2 path's.
+ * RGBD_ERR_UNSUPPORTED before any allocation: the ORB geometry's refusals for (width, height, scale_factor,
+ * nlevels), a level size that differs from cv::ORB's, nfeatures outside 1..8192, fast_threshold outside 1..255,
+ * edge_threshold outside 22..255 (22 = the descriptor's reach), cand_cap outside 0..12288, max_keypoints nonzero
+ * and below nfeatures. */
+typedef struct {
+    int32_t nfeatures;        /* 1000 */
+    float scale_factor;       /* 1.2f */
+    int32_t nlevels;          /* 8 */
+    int32_t edge_threshold;   /* 31 */
+    int32_t fast_threshold;   /* 20 */
+    int32_t cand_cap;         /* FAST corners stored per (frame, level) after the border filter; 0: 8192.  A frame with
+                                 a level that has more fails alone with RGBD_ERR_CAPACITY */
+    int32_t max_keypoints;    /* output capacity per frame; 0: nfeatures + nfeatures / 4.  retainBest keeps every tie of
+                                 its boundary response, so a frame may keep more than nfeatures; one that keeps more
+                                 than this fails alone with RGBD_ERR_CAPACITY */
+} rgbd_cvorb_params;
+rgbd_status rgbd_create_cvorb(int device, int width, int height, int max_batch, const rgbd_cvorb_params* params,
+                              const rgbd_camera* cam, rgbd_ctx** out);
+/* One level of frame b of the last batch, by stage:
+ *   0  *n = the FAST corners after the border filter (the count goes on past cand_cap); nothing else is written
+ *   1  the list after retainBest(2 N) in its order: xys[3 i ..] = (x, y, FAST score) in level coordinates
+ *   2  harris[i] = the Harris response of entry i of stage 1's list
+ *   3  the list after retainBest(N): xys and harris
+ * xys / harris may be null; cap = entries they hold (RGBD_ERR_CAPACITY when the list is longer, *n still set).
+ * On another kind of context: RGBD_ERR_ARG, "not a cv::ORB context". */
+rgbd_status rgbd_cvorb_debug_level(rgbd_ctx* ctx, int32_t b, int32_t level, int32_t stage, int32_t* xys, float* harris,
+                                   int32_t cap, int32_t* n);
+
 /* ------------------------------------------------------------------ matching */
 /* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}.
  * At most 65536 train rows (nt): the kernel's rank key holds the train index in 16 bits.  A larger nt

@@ -97,6 +97,21 @@ def gftt_params(nfeatures=1000, quality_level=0.01, min_distance=3.0, cand_cap=0
     return GfttParams(nfeatures, cand_cap, quality_level, min_distance)
 
 
+class CvorbParams(C.Structure):
+    """rgbd_cvorb_params: Extractor(ORB, ORB, NORMAL) (Features/Extractor.cpp:163-166, 216-218)."""
+    _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32),
+                ("edge_threshold", C.c_int32), ("fast_threshold", C.c_int32), ("cand_cap", C.c_int32),
+                ("max_keypoints", C.c_int32)]
+
+
+def cvorb_params(nfeatures=1000, scale_factor=1.2, nlevels=8, edge_threshold=31, fast_threshold=20, cand_cap=0,
+                 max_keypoints=0) -> CvorbParams:
+    """cv::ORB::create(nfeatures, scaleFactor, nlevels)'s values.  cand_cap 0 = 8192 stored FAST corners per (frame,
+    level), at most 12288; max_keypoints 0 = nfeatures + nfeatures / 4 (retainBest keeps ties).  A frame over
+    either raises RGBD_ERR_CAPACITY for that frame alone."""
+    return CvorbParams(nfeatures, scale_factor, nlevels, edge_threshold, fast_threshold, cand_cap, max_keypoints)
+
+
 class CloudParams(C.Structure):
     _fields_ = [("stride", C.c_int32), ("zmin", C.c_float), ("zmax", C.c_float), ("leaf", C.c_float),
                 ("sor_k", C.c_int32), ("sor_std", C.c_double)]
@@ -203,6 +218,9 @@ _SIGS = {
     "rgbd_gftt_debug_corners": (_i32, [_vp, _i32, C.POINTER(C.c_uint32), _PI, _vp, _vp, _i32, _PI]),
     "rgbd_gftt_debug_ranks": (_i32, [_vp, _i32, _PI]),
     "rgbd_gftt_select": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _i32, _i32, _vp, _PI]),
+    "rgbd_create_cvorb": (_i32, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CvorbParams), C.POINTER(Camera),
+                                 C.POINTER(_vp)]),
+    "rgbd_cvorb_debug_level": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _PI]),
     "rgbd_destroy": (None, [_vp]),
     "rgbd_last_error": (C.c_char_p, [_vp]),
     "rgbd_max_keypoints": (_i32, [_vp]),
@@ -427,20 +445,25 @@ class Context:
 
     def __init__(self, width=640, height=480, max_batch=1, orb: OrbParams | None = None,
                  cam: Camera | None = None, device=0, svo: SvoParams | None = None,
-                 adaptive: AdaptiveParams | None = None, gftt: GfttParams | None = None):
+                 adaptive: AdaptiveParams | None = None, gftt: GfttParams | None = None,
+                 cvorb: CvorbParams | None = None):
         """svo: an Extractor(SVO, BRIEF, NORMAL) context (rgbd_create_svo) instead of the ORBextractor;
         adaptive: an Extractor(FAST, BRIEF, ADAPTIVE) context (rgbd_create_adaptive);
-        gftt: an Extractor(GFTT, BRIEF, NORMAL) context (rgbd_create_gftt)."""
-        if (svo is not None) + (adaptive is not None) + (gftt is not None) > 1:
-            raise ValueError("Context: svo, adaptive and gftt are different extractors; give one")
+        gftt: an Extractor(GFTT, BRIEF, NORMAL) context (rgbd_create_gftt);
+        cvorb: an Extractor(ORB, ORB, NORMAL) context, OpenCV's ORB (rgbd_create_cvorb)."""
+        if (svo is not None) + (adaptive is not None) + (gftt is not None) + (cvorb is not None) > 1:
+            raise ValueError("Context: svo, adaptive, gftt and cvorb are different extractors; give one")
         self.orb = orb or orb_params()
         self.cam = cam or camera(535.4, 539.2, 320.1, 247.6)
         self.svo = svo
         self.adaptive = adaptive
         self.gftt = gftt
+        self.cvorb = cvorb
         self.W, self.H = width, height
         h = C.c_void_p()
-        if gftt is not None:
+        if cvorb is not None:
+            st = lib().rgbd_create_cvorb(device, width, height, max_batch, C.byref(cvorb), C.byref(self.cam), C.byref(h))
+        elif gftt is not None:
             st = lib().rgbd_create_gftt(device, width, height, max_batch, C.byref(gftt), C.byref(self.cam), C.byref(h))
         elif adaptive is not None:
             st = lib().rgbd_create_adaptive(device, width, height, max_batch, C.byref(adaptive), C.byref(self.cam),
@@ -579,6 +602,26 @@ class Context:
         self._check(lib().rgbd_gftt_select(self._h, _ptr(xy), _ptr(val), len(xy), W, H, float(min_distance), max_corners,
                                            chunk, _ptr(out), C.byref(m)), "gftt_select")
         return out[:m.value].copy()
+
+    # --- OpenCV ORB (rgbd_create_cvorb contexts)
+    def cvorb_debug_level(self, b: int, level: int):
+        """One level of frame b of the last batch: dict(n_fast = FAST corners after the border filter (it counts past
+        cand_cap), s1 [n1, 3] int32 (x, y, score) after retainBest(2 N) in its order, h1 [n1] f32 their Harris
+        responses, s2 [n2, 3] / h2 [n2] after retainBest(N))."""
+        cap = (self.cvorb.cand_cap or 8192) if self.cvorb is not None else 1
+        n = C.c_int32(0)
+        out = {}
+        self._check(lib().rgbd_cvorb_debug_level(self._h, b, level, 0, None, None, 0, C.byref(n)), "cvorb_debug_level")
+        out["n_fast"] = n.value
+        xys = np.zeros((cap, 3), np.int32)
+        hr = np.zeros(cap, np.float32)
+        self._check(lib().rgbd_cvorb_debug_level(self._h, b, level, 1, _ptr(xys), None, cap, C.byref(n)), "cvorb_debug_level")
+        out["s1"] = xys[:n.value].copy()
+        self._check(lib().rgbd_cvorb_debug_level(self._h, b, level, 2, None, _ptr(hr), cap, C.byref(n)), "cvorb_debug_level")
+        out["h1"] = hr[:n.value].copy()
+        self._check(lib().rgbd_cvorb_debug_level(self._h, b, level, 3, _ptr(xys), _ptr(hr), cap, C.byref(n)), "cvorb_debug_level")
+        out["s2"], out["h2"] = xys[:n.value].copy(), hr[:n.value].copy()
+        return out
 
     # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive and GFTT contexts)
     def set_brief_pattern(self, pairs: np.ndarray):

@@ -105,7 +105,7 @@ static rgbd_status mark_extracted(rgbd_ctx* c)
 rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
                         const rgbd::ExtractHook* after_fast = nullptr)
 {
-    // per-frame capacity flags (k_distribute / k_svo_select / k_adp_select / k_gftt_cand), cleared for every extraction
+    // per-frame capacity flags (k_distribute / k_svo_select / k_adp_select / k_gftt_cand / k_cvorb_list / k_cvorb_frame), cleared for every extraction
     rgbd_status s0 = check_hip(c, hipMemsetAsync(c->d_err, 0, sizeof(int) * (size_t)B, c->stream), "clear err");
     if (s0) return s0;
     if (c->adaptive) {
@@ -114,6 +114,10 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
     }
     if (c->gftt) {
         if ((s0 = gftt_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
+        return mark_extracted(c);
+    }
+    if (c->cvorb) {
+        if ((s0 = cvorb_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
         return mark_extracted(c);
     }
     if (c->svo) {
@@ -220,7 +224,7 @@ rgbd_status upload_table(rgbd_ctx* c, DevBuf<D>& d, const std::vector<T>& v, con
 
 rgbd_status create_ctx(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
                        const rgbd_svo_params* svo, const rgbd_adaptive_params* adp, const rgbd_gftt_params* gftt,
-                       const rgbd_camera* cam, rgbd_ctx** out)
+                       const rgbd_cvorb_params* cvorb, const rgbd_camera* cam, rgbd_ctx** out)
 {
     if (!out || !orb || !cam || max_batch < 1) return RGBD_ERR_ARG;
     rgbd_ctx* c = new rgbd_ctx();
@@ -243,8 +247,13 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
         const rgbd_status sg = gftt_configure(c, *gftt);   // likewise
         if (sg) return sg;
     }
+    if (cvorb) {
+        const rgbd_status sc = cvorb_check_params(c, *cvorb);
+        if (sc) return sc;
+    }
     if (s) return s;
     if (svo && (s = svo_configure(c, *svo))) return s;   // sets cfg.kp_cap before the allocations
+    if (cvorb && (s = cvorb_configure(c, *cvorb))) return s;   // likewise, from the accepted geometry
     if ((s = check_hip(c, hipSetDevice(device), "hipSetDevice"))) return s;
     if ((s = check_hip(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking), "stream"))) return s;
     c->stream = c->own_stream;
@@ -296,6 +305,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (!s && svo) s = svo_alloc(c);
     if (!s && adp) s = adaptive_alloc(c);
     if (!s && gftt) s = gftt_alloc(c);
+    if (!s && cvorb) s = cvorb_alloc(c);
     return s;
 }
 
@@ -306,7 +316,7 @@ extern "C" {
 rgbd_status rgbd_create(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
                         const rgbd_camera* cam, rgbd_ctx** out)
 {
-    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, const rgbd_svo_params* svo,
@@ -317,7 +327,7 @@ rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, co
     // fields only shape the scale tables the reference's getters report (the ORB workspace is never run,
     // so its budget is kept small)
     const rgbd_orb_params orb{std::max(1, std::min(svo->nfeatures, 1000)), 1.2f, 8, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batch, const rgbd_adaptive_params* params,
@@ -327,7 +337,7 @@ rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batc
     // the ORB workspace is never run: a one-level ORB geometry (every adaptive keypoint has octave 0), so of the
     // ORB shape refusals only level 0's remain (the 8-level geometry refuses e.g. 320 x 256 for its level 7)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, const rgbd_gftt_params* params,
@@ -336,7 +346,17 @@ rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, c
     if (!params) return RGBD_ERR_ARG;
     // as for rgbd_create_adaptive: a one-level ORB geometry that is never run (every GFTT keypoint has octave 0)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, params, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, params, nullptr, cam, out);
+}
+
+rgbd_status rgbd_create_cvorb(int device, int width, int height, int max_batch, const rgbd_cvorb_params* params,
+                              const rgbd_camera* cam, rgbd_ctx** out)
+{
+    if (!params) return RGBD_ERR_ARG;
+    // the ORB geometry of the caller's pyramid: its k_pyramid and blur run; its FAST cells and quadtree never do, so
+    // their budget is kept small (as for rgbd_create_svo)
+    const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), params->scale_factor, params->nlevels, 20, 7};
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, nullptr, params, cam, out);
 }
 
 void rgbd_destroy(rgbd_ctx* c)
@@ -357,6 +377,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::svo_free(c);
     rgbd::adaptive_free(c);
     rgbd::gftt_free(c);
+    rgbd::cvorb_free(c);
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     const hipStream_t own = c->own_stream, solve = c->solve_stream, match = c->match_stream;

@@ -11,7 +11,7 @@
 #include "rgbd_internal.h"
 
 namespace rgbd {
-struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS; struct GfttWS;
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS; struct GfttWS; struct CvorbWS;
 // the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
 struct OutSet {
     int* count = nullptr;
@@ -90,6 +90,7 @@ struct rgbd_ctx {
     rgbd::SvoWS* svo = nullptr;          // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
     rgbd::AdpWS* adaptive = nullptr;     // adaptive FAST + BRIEF extractor (adaptive_host.cpp); takes precedence over svo
     rgbd::GfttWS* gftt = nullptr;        // Shi-Tomasi GFTT + BRIEF extractor (gftt_host.cpp); a context has at most one of svo / adaptive / gftt
+    rgbd::CvorbWS* cvorb = nullptr;      // OpenCV ORB extractor (cvorb_host.cpp); likewise exclusive
     rgbd::ProjWS* proj = nullptr;        // projection-guided matching (project_host.cpp)
     rgbd::BaWS* pnpba = nullptr;         // motion-only bundle adjustment, PnPSolver (pnpba_host.cpp)
     rgbd::UmWS* umeyama = nullptr;       // Umeyama RANSAC, Ransac (umeyama_host.cpp)
@@ -121,6 +122,8 @@ rgbd_status fail(rgbd_ctx* c, rgbd_status code, const std::string& msg);
 // what a frame's extraction flag (rgbd_ctx::d_err, nonzero) says, for RGBD_ERR_CAPACITY: one wording on every path
 inline const char* extract_flag_message(int flag)
 {
+    if (flag & 32) return "cv::ORB: the frame keeps more keypoints than max_keypoints (retainBest keeps ties)";
+    if (flag & 16) return "cv::ORB: a level has more FAST corners than cand_cap stores";
     if (flag & 8) return "gftt: the frame has more candidates than cand_cap stores";
     if (flag & 4) return "adaptive: a cell has more corners at its threshold than cell_cap stores";
     if (flag & 2) return "SVO: keypoints kept by retainBest exceed rgbd_max_keypoints";
@@ -179,4 +182,12 @@ rgbd_status gftt_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* 
 uint8_t* gftt_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
 rgbd_status gftt_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
 rgbd_status gftt_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
+// cvorb_host.cpp: the Extractor(ORB, ORB, NORMAL) front end of an rgbd_create_cvorb context (it runs on the ORB
+// geometry's pyramid, so the gray upload target is the ORBextractor's)
+rgbd_status cvorb_check_params(rgbd_ctx* c, const rgbd_cvorb_params& p);   // the parameter refusals, before the geometry's
+rgbd_status cvorb_configure(rgbd_ctx* c, const rgbd_cvorb_params& p);      // on an accepted geometry; before the output allocations
+rgbd_status cvorb_alloc(rgbd_ctx* c);
+void cvorb_free(rgbd_ctx* c);
+rgbd_status cvorb_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                              const ExtractHook* after_fast);
 }  // namespace rgbd

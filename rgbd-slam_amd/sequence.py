@@ -39,7 +39,8 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
       - "orb": Extractor(ORB2, ORB2, NORMAL);
       - "svo": SVO + BRIEF, the reference's default;
       - "adaptive": FAST + BRIEF, ADAPTIVE;
-      - "gftt": Shi-Tomasi GFTT + BRIEF, NORMAL (no state between frames).
+      - "gftt": Shi-Tomasi GFTT + BRIEF, NORMAL (no state between frames);
+      - "cvorb": Extractor(ORB, ORB, NORMAL), OpenCV's ORB (no state between frames; cand_cap at its bound).
     The adaptive extractor's per-cell thresholds are state: before every later batch they are rewound on the device by the batches' overlap (1 frame with pnp, 2 with se3), so the
     frames a batch repeats start from the thresholds they started from the first time."""
     import torch
@@ -57,8 +58,11 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
         ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, adaptive=pkg.adaptive_params(nfeatures))
     elif extractor == "gftt":
         ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device, gftt=pkg.gftt_params(nfeatures))
+    elif extractor == "cvorb":
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device,
+                          cvorb=pkg.cvorb_params(nfeatures, cand_cap=12288))
     else:
-        raise ValueError(f"extractor must be 'orb', 'svo', 'adaptive' or 'gftt', not {extractor!r}")
+        raise ValueError(f"extractor must be 'orb', 'svo', 'adaptive', 'gftt' or 'cvorb', not {extractor!r}")
     adaptive = extractor == "adaptive"
     dev = torch.device("cuda", device)
     poses = np.zeros((n, 4, 4), np.float32)
