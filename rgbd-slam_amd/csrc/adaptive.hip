@@ -17,52 +17,16 @@
 #include <cstdint>
 
 #include "adaptive_dev.h"
+#include "fast_tile_dev.h"
 #include "select_dev.h"
 
 namespace rgbd {
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------ the threshold-free FAST-9 score map
 constexpr int kScTW = 64, kScTH = 32;
 constexpr int kScHy = 3, kScHx = 8;                 // staged halo: 3 rows, 8 columns (dword-aligned)
 constexpr int kScGW = kScTW + 2 * kScHx;            // 80 staged columns: x0-8 .. x0+71
 constexpr int kScGH = kScTH + 2 * kScHy;            // 38 staged rows: y0-3 .. y0+34
-
-// M of two horizontally adjacent pixels at once (packed u16 lanes): the largest, over the 16 nine-pixel arcs
-// of the ring, of min(x - v) (brighter) or min(v - x) (darker), clamped at 0 by the saturating subtraction
-__device__ __forceinline__ u16x2 fast9_m2(const uint32_t* P, int S, int r, int c)
-{
-    const uint32_t* p = P + r * S + c;
-    uint32_t raw[16];
-    raw[0] = p[3 * S];       raw[1] = p[3 * S + 1];   raw[2] = p[2 * S + 2];   raw[3] = p[1 * S + 3];
-    raw[4] = p[3];           raw[5] = p[-1 * S + 3];  raw[6] = p[-2 * S + 2];  raw[7] = p[-3 * S + 1];
-    raw[8] = p[-3 * S];      raw[9] = p[-3 * S - 1];  raw[10] = p[-2 * S - 2]; raw[11] = p[-1 * S - 3];
-    raw[12] = p[-3];         raw[13] = p[1 * S - 3];  raw[14] = p[2 * S - 2];  raw[15] = p[3 * S - 1];
-    const u16x2 v = __builtin_bit_cast(u16x2, p[0]);
-    u16x2 x[16], mn2[16], mx2[16], mn4[16], mx4[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) x[k] = __builtin_bit_cast(u16x2, raw[k]);
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        mn2[k] = __builtin_elementwise_min(x[k], x[(k + 1) & 15]);
-        mx2[k] = __builtin_elementwise_max(x[k], x[(k + 1) & 15]);
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        mn4[k] = __builtin_elementwise_min(mn2[k], mn2[(k + 2) & 15]);
-        mx4[k] = __builtin_elementwise_max(mx2[k], mx2[(k + 2) & 15]);
-    }
-    u16x2 MM = {0xffff, 0xffff}, mm = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 16; k++) {   // arc k .. k+8 = (k .. k+3), (k+4 .. k+7) and k+8
-        const u16x2 amin = __builtin_elementwise_min(__builtin_elementwise_min(mn4[k], mn4[(k + 4) & 15]), x[(k + 8) & 15]);
-        const u16x2 amax = __builtin_elementwise_max(__builtin_elementwise_max(mx4[k], mx4[(k + 4) & 15]), x[(k + 8) & 15]);
-        mm = __builtin_elementwise_max(mm, amin);
-        MM = __builtin_elementwise_min(MM, amax);
-    }
-    return __builtin_elementwise_max(__builtin_elementwise_sub_sat(v, MM), __builtin_elementwise_sub_sat(mm, v));
-}
 
 // One 256-thread workgroup per 64 x 32 tile of a frame's gray image: S = max(M, 1) - 1 where the ring lies in
 // the image (x in [3, W-3), y in [3, H-3)), else 0.

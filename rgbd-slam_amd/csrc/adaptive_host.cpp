@@ -1,7 +1,7 @@
 // adaptive_host.cpp -- host side of the adaptive FAST + BRIEF front end (adaptive.hip): Extractor(FAST, BRIEF,
 // ADAPTIVE), behind the same extraction entry points as the ORBextractor and the SVO front end.
 //   Extractor::createAdaptiveDetector Features/Extractor.cpp:82-109  -> adaptive_configure (AdpCfg, derived counts)
-//   Extractor::detectAndCompute       Features/Extractor.cpp:50-61   -> adaptive_run_extract (one launch chain)
+//   Extractor::detectAndCompute       Features/Extractor.cpp:50-61   -> AdpWS::run (one launch chain)
 //   Frame::undistortKeyPoints + uprojectCamera (Core/Frame.cpp:91-117, 251-281) -> k_undistort
 #include <hip/hip_runtime.h>
 
@@ -11,17 +11,14 @@
 #include <vector>
 
 #include "adaptive_dev.h"
-#include "context.h"
+#include "brief_front.h"
 #include "launch.h"
-#include "svo_dev.h"
 
 namespace rgbd {
 
-struct AdpWS {
+struct AdpWS : FrontEnd {
     AdpCfg cfg{};
-    SvoCfg pyr{};                 // k_svo_pyramid (one level: gray + box sums) and k_svo_brief
-    DevBuf<uint8_t> d_gray;       // [B][frame_bytes]
-    DevBuf<uint16_t> d_box;       // [B][H][W]
+    BriefFront bf;                // one level: gray + box sums
     DevBuf<uint8_t> d_smap;       // [B][H][W]
     DevBuf<uint32_t> d_list;      // [B][ncells][cell_cap]
     DevBuf<int> d_nlist;          // [B][ncells]
@@ -31,30 +28,19 @@ struct AdpWS {
     DevBuf<int> d_used, d_tries;  // [B][ncells]
     DevBuf<uint32_t> d_sel;       // [B][ncells][max_per_cell]
     DevBuf<int> d_nsel;           // [B][ncells]
-    DevBuf<uint32_t> d_pat;
     DevBuf<float> d_kt_resp;      // rgbd_adaptive_keep_strongest staging
     DevBuf<int> d_kt_order;
     double init_thresh = 20.0;
-    int8_t pattern[256 * 4];
+
+    rgbd_status alloc(rgbd_ctx* c) override;
+    rgbd_status run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                    const ExtractHook* after_fast) override;
+    BriefFront* brief() override { return &bf; }
 };
 
 namespace {
 
-const int8_t kDefaultBrief[256 * 4] = {
-#include "brief_pattern.inc"
-};
-
-AdpWS* ws(rgbd_ctx* c) { return c->adaptive; }
-
-rgbd_status upload_pattern(rgbd_ctx* c, AdpWS* w)
-{
-    uint32_t packed[256];
-    for (int t = 0; t < 256; t++) {
-        const uint8_t* q = reinterpret_cast<const uint8_t*>(w->pattern + 4 * t);
-        packed[t] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
-    return check_hip(c, hipMemcpyAsync(w->d_pat, packed, sizeof(packed), hipMemcpyHostToDevice, c->stream), "brief pattern");
-}
+AdpWS* ws(rgbd_ctx* c) { return dynamic_cast<AdpWS*>(c->front.get()); }   // null: not an adaptive context
 
 rgbd_status not_adaptive(rgbd_ctx* c) { return fail(c, RGBD_ERR_ARG, "not an adaptive context (rgbd_create_adaptive)"); }
 
@@ -99,114 +85,67 @@ rgbd_status adaptive_configure(rgbd_ctx* c, const rgbd_adaptive_params& p)
     g.kp_cap = g.ncells * g.max_per_cell;
     g.cell_cap = cap;
     g.tmin = std::max(1, (int)p.min_thresh);
-    g.border = 48 / 2 + 9 / 2;                            // BriefDescriptorExtractorImpl PATCH_SIZE, KERNEL_SIZE
+    g.border = kBriefBorder;
     g.min_thresh = p.min_thresh;
     g.max_thresh = p.max_thresh;
     g.increase = p.increase;
     g.decrease = p.decrease;
     AdpWS* w = new AdpWS();
-    c->adaptive = w;
+    c->front.reset(w);
     w->cfg = g;
     w->init_thresh = p.init_thresh;
-    SvoCfg& s = w->pyr;
-    s.W = c->W;
-    s.H = c->H;
-    s.nlevels = 1;
-    s.lw[0] = c->W;
-    s.lh[0] = c->H;
-    s.loff[0] = 0;
-    s.frame_bytes = (c->W * c->H + 63) & ~63;
-    s.kp_cap = g.kp_cap;
-    s.border = g.border;
-    std::memcpy(w->pattern, kDefaultBrief, sizeof(kDefaultBrief));
+    w->bf.one_level(c->W, c->H, g.kp_cap);
     c->cfg.kp_cap = g.kp_cap;   // the output arrays (kps, desc, xyz, knn) are sized by it
     return RGBD_OK;
 }
 
-rgbd_status adaptive_alloc(rgbd_ctx* c)
+rgbd_status AdpWS::alloc(rgbd_ctx* c)
 {
-    AdpWS* w = ws(c);
-    const AdpCfg& g = w->cfg;
+    const AdpCfg& g = cfg;
     const size_t B = (size_t)c->maxB, nc = (size_t)g.ncells;
-    rgbd_status s = check_hip(c, w->d_gray.alloc(B * w->pyr.frame_bytes + 64), "adaptive gray");
-    if (!s) s = check_hip(c, w->d_box.alloc(B * g.W * g.H), "adaptive box");
-    if (!s) s = check_hip(c, w->d_smap.alloc(B * g.W * g.H), "adaptive score map");
-    if (!s) s = check_hip(c, w->d_list.alloc(B * nc * g.cell_cap), "adaptive cell lists");
-    if (!s) s = check_hip(c, w->d_nlist.alloc(B * nc), "adaptive list counts");
-    if (!s) s = check_hip(c, w->d_nge.alloc(B * nc * 256), "adaptive suffix counts");
-    if (!s) s = check_hip(c, w->d_state.alloc(nc), "adaptive thresholds");
-    if (!s) s = check_hip(c, w->d_before.alloc(B * nc), "adaptive thresholds before");
-    if (!s) s = check_hip(c, w->d_used.alloc(B * nc), "adaptive thresholds used");
-    if (!s) s = check_hip(c, w->d_tries.alloc(B * nc), "adaptive tries");
-    if (!s) s = check_hip(c, w->d_sel.alloc(B * nc * g.max_per_cell), "adaptive cell survivors");
-    if (!s) s = check_hip(c, w->d_nsel.alloc(B * nc), "adaptive survivor counts");
-    if (!s) s = check_hip(c, w->d_pat.alloc(256), "adaptive pattern");
+    rgbd_status s = bf.alloc(c, "adaptive", "gray");
+    if (!s) s = check_hip(c, d_smap.alloc(B * g.W * g.H), "adaptive score map");
+    if (!s) s = check_hip(c, d_list.alloc(B * nc * g.cell_cap), "adaptive cell lists");
+    if (!s) s = check_hip(c, d_nlist.alloc(B * nc), "adaptive list counts");
+    if (!s) s = check_hip(c, d_nge.alloc(B * nc * 256), "adaptive suffix counts");
+    if (!s) s = check_hip(c, d_state.alloc(nc), "adaptive thresholds");
+    if (!s) s = check_hip(c, d_before.alloc(B * nc), "adaptive thresholds before");
+    if (!s) s = check_hip(c, d_used.alloc(B * nc), "adaptive thresholds used");
+    if (!s) s = check_hip(c, d_tries.alloc(B * nc), "adaptive tries");
+    if (!s) s = check_hip(c, d_sel.alloc(B * nc * g.max_per_cell), "adaptive cell survivors");
+    if (!s) s = check_hip(c, d_nsel.alloc(B * nc), "adaptive survivor counts");
     if (s) return s;
-    std::vector<double> init(nc, w->init_thresh);
-    s = check_hip(c, hipMemcpy(w->d_state, init.data(), nc * 8, hipMemcpyHostToDevice), "adaptive thresholds up");
-    if (!s) s = upload_pattern(c, w);
+    std::vector<double> init(nc, init_thresh);
+    s = check_hip(c, hipMemcpy(d_state, init.data(), nc * 8, hipMemcpyHostToDevice), "adaptive thresholds up");
     if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "sync");
     return s;
 }
 
-void adaptive_free(rgbd_ctx* c)
+rgbd_status AdpWS::run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                       const ExtractHook* after_fast)
 {
-    delete c->adaptive;
-    c->adaptive = nullptr;
-}
-
-uint8_t* adaptive_gray_level(rgbd_ctx* c) { return ws(c)->d_gray; }
-
-rgbd_status adaptive_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                                 const ExtractHook* after_fast)
-{
-    AdpWS* w = ws(c);
-    const AdpCfg& g = w->cfg;
+    const AdpCfg& g = cfg;
     const hipStream_t st = c->stream;
-    int tk = timer_begin(c, "k_svo_pyramid");
-    RGBD_TRY(c, launch_svo_pyramid(from_gray ? nullptr : d_bgr, w->d_gray, w->d_box, w->pyr, B, st), "svo_pyramid");
-    timer_end(c, tk);
-    tk = timer_begin(c, "k_adp_score");
-    RGBD_TRY(c, launch_adp_score(w->d_gray, (size_t)w->pyr.frame_bytes, w->d_smap, g, B, st), "adp_score");
+    rgbd_status s = bf.run_pyramid(c, d_bgr, B, from_gray);
+    if (s) return s;
+    int tk = timer_begin(c, "k_adp_score");
+    RGBD_TRY(c, launch_adp_score(bf.d_pyr, (size_t)bf.cfg.frame_bytes, d_smap, g, B, st), "adp_score");
     timer_end(c, tk);
     tk = timer_begin(c, "k_adp_cells");
-    RGBD_TRY(c, launch_adp_cells(w->d_smap, g, w->d_list, w->d_nlist, w->d_nge, B, st), "adp_cells");
+    RGBD_TRY(c, launch_adp_cells(d_smap, g, d_list, d_nlist, d_nge, B, st), "adp_cells");
     timer_end(c, tk);
-    if (after_fast) {   // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
-        rgbd_status hs = (*after_fast)(1);
-        if (!hs) hs = (*after_fast)(2);
-        if (hs) return hs;
-    }
+    // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
+    if ((s = call_hook(after_fast, 1)) || (s = call_hook(after_fast, 2))) return s;
     tk = timer_begin(c, "k_adp_chain");
-    RGBD_TRY(c, launch_adp_chain(w->d_nge, g, w->d_state, w->d_before, w->d_used, w->d_tries, B, st), "adp_chain");
+    RGBD_TRY(c, launch_adp_chain(d_nge, g, d_state, d_before, d_used, d_tries, B, st), "adp_chain");
     timer_end(c, tk);
     tk = timer_begin(c, "k_adp_select");
-    RGBD_TRY(c, launch_adp_select(w->d_list, w->d_nlist, w->d_nge, w->d_used, g, w->d_sel, w->d_nsel, c->d_err, B, st), "adp_select");
+    RGBD_TRY(c, launch_adp_select(d_list, d_nlist, d_nge, d_used, g, d_sel, d_nsel, c->d_err, B, st), "adp_select");
     timer_end(c, tk);
     tk = timer_begin(c, "k_adp_frame");
-    RGBD_TRY(c, launch_adp_frame(w->d_sel, w->d_nsel, g, c->out.count, c->out.kps, B, st), "adp_frame");
+    RGBD_TRY(c, launch_adp_frame(d_sel, d_nsel, g, c->out.count, c->out.kps, B, st), "adp_frame");
     timer_end(c, tk);
-    tk = timer_begin(c, "k_svo_brief");
-    RGBD_TRY(c, launch_svo_brief(w->d_box, c->out.count, c->out.kps, w->d_pat, w->pyr, c->out.desc, B, st), "svo_brief");
-    timer_end(c, tk);
-    tk = timer_begin(c, "k_undistort");
-    RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, g.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
-    timer_end(c, tk);
-    c->last_B = B;
-    return RGBD_OK;
-}
-
-rgbd_status adaptive_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs)
-{
-    std::memcpy(ws(c)->pattern, pairs, 1024);
-    rgbd_status s = upload_pattern(c, ws(c));
-    return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "sync");
-}
-
-rgbd_status adaptive_get_brief_pattern(rgbd_ctx* c, int8_t* pairs)
-{
-    std::memcpy(pairs, ws(c)->pattern, 1024);
-    return RGBD_OK;
+    return bf.run_describe(c, d_depth, B);
 }
 
 }  // namespace rgbd
@@ -218,7 +157,7 @@ extern "C" {
 rgbd_status rgbd_adaptive_get_thresholds(rgbd_ctx* c, double* thresh)
 {
     if (!c || !thresh) return RGBD_ERR_ARG;
-    if (!c->adaptive) return not_adaptive(c);
+    if (!ws(c)) return not_adaptive(c);
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (!s) s = check_hip(c, hipMemcpyAsync(thresh, ws(c)->d_state, (size_t)ws(c)->cfg.ncells * 8, hipMemcpyDeviceToHost, c->stream),
                           "read thresholds");
@@ -228,7 +167,7 @@ rgbd_status rgbd_adaptive_get_thresholds(rgbd_ctx* c, double* thresh)
 rgbd_status rgbd_adaptive_set_thresholds(rgbd_ctx* c, const double* thresh)
 {
     if (!c || !thresh) return RGBD_ERR_ARG;
-    if (!c->adaptive) return not_adaptive(c);
+    if (!ws(c)) return not_adaptive(c);
     const AdpCfg& g = ws(c)->cfg;
     for (int k = 0; k < g.ncells; k++)
         if (!(thresh[k] >= g.min_thresh && thresh[k] <= g.max_thresh))
@@ -242,7 +181,7 @@ rgbd_status rgbd_adaptive_set_thresholds(rgbd_ctx* c, const double* thresh)
 rgbd_status rgbd_adaptive_rewind(rgbd_ctx* c, int32_t k)
 {
     if (!c) return RGBD_ERR_ARG;
-    if (!c->adaptive) return not_adaptive(c);
+    if (!ws(c)) return not_adaptive(c);
     if (k < 1 || k > c->last_B) return fail(c, RGBD_ERR_ARG, "adaptive: rewind by 1 .. the last batch's frames");
     AdpWS* w = ws(c);
     const size_t nc = (size_t)w->cfg.ncells;
@@ -255,7 +194,7 @@ rgbd_status rgbd_adaptive_rewind(rgbd_ctx* c, int32_t k)
 rgbd_status rgbd_adaptive_debug_cell(rgbd_ctx* c, int32_t b, int32_t cell, uint64_t* thresh_before_bits, int32_t* thresh_used,
                                      int32_t* tries, int32_t* xys, int32_t cap, int32_t* n)
 {
-    if (!c || !c->adaptive || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
+    if (!c || !ws(c) || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
     AdpWS* w = ws(c);
     const AdpCfg& g = w->cfg;
     if (cell < 0 || cell >= g.ncells || cap < 0) return RGBD_ERR_ARG;
@@ -298,7 +237,7 @@ rgbd_status rgbd_adaptive_keep_strongest(rgbd_ctx* c, const float* resp, int32_t
                                          int32_t* order)
 {
     if (!c || !order || n < 0 || N < 0 || (n > 0 && !resp)) return RGBD_ERR_ARG;
-    if (!c->adaptive) return not_adaptive(c);
+    if (!ws(c)) return not_adaptive(c);
     if (n > kAdpSelMax) return fail(c, RGBD_ERR_UNSUPPORTED, "keepStrongest: n <= 12288");
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;

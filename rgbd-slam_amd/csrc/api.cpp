@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "context.h"
+#include "brief_front.h"
 #include "geometry.h"
 #include "launch.h"
 
@@ -87,6 +87,28 @@ void timer_flush(rgbd_ctx* c)
     c->pending.clear();
 }
 
+rgbd_status run_orb_pyramid(rgbd_ctx* c, const uint8_t* d_bgr, int B, bool from_gray)
+{
+    const ExtractCfg& C = c->cfg;
+    const hipStream_t st = c->stream;
+    int tk;
+    if (C.nlevels > 1) {   // k_pyramid converts BGR -> gray (level 0) itself unless given a gray level 0
+        tk = timer_begin(c, "k_pyramid");
+        RGBD_TRY(c, launch_pyramid(c->d_pyr, from_gray ? nullptr : d_bgr, c->d_rsy, c->d_qx, c->d_cfg, C.pyr_lds + C.pyr_rsy_lds, B, st), "pyramid");
+        timer_end(c, tk);
+        if (C.pyr_top < C.nlevels) {   // the small levels after the strips
+            tk = timer_begin(c, "k_pyr_tail");
+            RGBD_TRY(c, launch_pyr_tail(c->d_pyr, c->d_rsy, c->d_qx, c->d_cfg, B, st), "pyramid tail");
+            timer_end(c, tk);
+        }
+    } else if (!from_gray) {
+        tk = timer_begin(c, "k_gray");
+        RGBD_TRY(c, launch_gray(d_bgr, c->d_pyr, C.W, C.H, C.frame_pyr_bytes, B, st), "gray");
+        timer_end(c, tk);
+    }
+    return RGBD_OK;
+}
+
 }  // namespace rgbd
 
 namespace {
@@ -105,49 +127,22 @@ static rgbd_status mark_extracted(rgbd_ctx* c)
 rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
                         const rgbd::ExtractHook* after_fast = nullptr)
 {
-    // per-frame capacity flags (k_distribute / k_svo_select / k_adp_select / k_gftt_cand / k_cvorb_list / k_cvorb_frame), cleared for every extraction
+    // per-frame capacity flags (k_distribute and the front ends' kernels: extract_flag_message), cleared for every extraction
     rgbd_status s0 = check_hip(c, hipMemsetAsync(c->d_err, 0, sizeof(int) * (size_t)B, c->stream), "clear err");
     if (s0) return s0;
-    if (c->adaptive) {
-        if ((s0 = adaptive_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
-        return mark_extracted(c);
-    }
-    if (c->gftt) {
-        if ((s0 = gftt_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
-        return mark_extracted(c);
-    }
-    if (c->cvorb) {
-        if ((s0 = cvorb_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
-        return mark_extracted(c);
-    }
-    if (c->svo) {
-        if ((s0 = svo_run_extract(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
+    if (c->front) {
+        if ((s0 = c->front->run(c, d_bgr, d_depth, B, from_gray, after_fast))) return s0;
         return mark_extracted(c);
     }
     ExtractCfg& C = c->cfg;
     hipStream_t st = c->stream;
-    int tk;
-    if (C.nlevels > 1) {   // k_pyramid converts BGR -> gray (level 0) itself unless given a gray level 0
-        tk = timer_begin(c, "k_pyramid");
-        RGBD_TRY(c, launch_pyramid(c->d_pyr, from_gray ? nullptr : d_bgr, c->d_rsy, c->d_qx, c->d_cfg, C.pyr_lds + C.pyr_rsy_lds, B, st), "pyramid");
-        timer_end(c, tk);
-        if (C.pyr_top < C.nlevels) {   // the small levels after the strips
-            tk = timer_begin(c, "k_pyr_tail");
-            RGBD_TRY(c, launch_pyr_tail(c->d_pyr, c->d_rsy, c->d_qx, c->d_cfg, B, st), "pyramid tail");
-            timer_end(c, tk);
-        }
-    } else if (!from_gray) {
-        tk = timer_begin(c, "k_gray");
-        RGBD_TRY(c, launch_gray(d_bgr, c->d_pyr, C.W, C.H, C.frame_pyr_bytes, B, st), "gray");
-        timer_end(c, tk);
-    }
-    auto hook = [&](int at) -> rgbd_status { return after_fast ? (*after_fast)(at) : RGBD_OK; };
-    rgbd_status hs;
-    if ((hs = hook(0))) return hs;
+    rgbd_status hs = run_orb_pyramid(c, d_bgr, B, from_gray);
+    if (hs) return hs;
+    if ((hs = call_hook(after_fast, 0))) return hs;
     // every level is blurred by each frame's leading blocks of the k_fast grid (blur_tile_walk's tile waves,
     // then blur_thread for the levels below the tile path's floor and for 1-level pyramids), so blur and FAST
     // waves share the CUs inside one launch
-    tk = timer_begin(c, "k_fast");
+    int tk = timer_begin(c, "k_fast");
 #ifdef RGBD_PNP_PROFILE
     // profiling build: RGBD_PROF_FAST_SPLIT=1 dispatches the grid's blur blocks and its FAST segments as two
     // k_fast launches (blur-only grid first), so per-dispatch counters give the blur's share of the launch
@@ -162,12 +157,12 @@ rgbd_status run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_dep
                 C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels], c->d_blur_tab, C.blur_m0[kMaxLevels]), "fast");
     timer_end(c, tk);
     // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
-    if ((hs = hook(1))) return hs;
+    if ((hs = call_hook(after_fast, 1))) return hs;
     tk = timer_begin(c, "k_distribute");
     RGBD_TRY(c, launch_distribute(c->d_cellc, c->d_slots, c->d_cfg, C.node_cap, C.scan_cap, 0, C.nlevels, C.dist_kc, c->d_keys,
                       c->d_node, c->d_selc, c->d_sel, c->d_err, c->d_dist_path, B, st), "distribute");
     timer_end(c, tk);
-    if ((hs = hook(2))) return hs;
+    if ((hs = call_hook(after_fast, 2))) return hs;
 #ifdef RGBD_PNP_PROFILE
     pyr_prof_dump(st);
     fprintf(stderr, "[pyr_lds] %d bytes per workgroup (odd levels at %d)\n", C.pyr_lds, C.pyr_lds_b);
@@ -302,10 +297,7 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     s = check_hip(c, hipMemset(c->d_err, 0, sizeof(int) * B), "memset err");
     if (!s) s = check_hip(c, hipMemset(c->d_pyr, 0, B * C.frame_pyr_bytes + 64), "memset pyr");
     if (!s) s = check_hip(c, hipMemset(c->d_blur, 0, B * C.frame_pyr_bytes + 64), "memset blur");
-    if (!s && svo) s = svo_alloc(c);
-    if (!s && adp) s = adaptive_alloc(c);
-    if (!s && gftt) s = gftt_alloc(c);
-    if (!s && cvorb) s = cvorb_alloc(c);
+    if (!s && c->front) s = c->front->alloc(c);
     return s;
 }
 
@@ -374,10 +366,7 @@ void rgbd_destroy(rgbd_ctx* c)
     rgbd::pnpba_free(c);
     rgbd::umeyama_free(c);
     rgbd::bow_free(c);
-    rgbd::svo_free(c);
-    rgbd::adaptive_free(c);
-    rgbd::gftt_free(c);
-    rgbd::cvorb_free(c);
+    c->front.reset();
     for (auto& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     const hipStream_t own = c->own_stream, solve = c->solve_stream, match = c->match_stream;
@@ -433,18 +422,10 @@ rgbd_status rgbd_detect_and_compute(rgbd_ctx* c, const uint8_t* gray, int32_t st
     if (step < c->W) return fail(c, RGBD_ERR_ARG, "step < width");
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
-    if (c->adaptive)
-        s = check_hip(c, hipMemcpy2DAsync(adaptive_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
-                      "upload gray");
-    else if (c->gftt)
-        s = check_hip(c, hipMemcpy2DAsync(gftt_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
-                      "upload gray");
-    else if (c->svo)
-        s = check_hip(c, hipMemcpy2DAsync(svo_gray_level(c), c->W, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
-                      "upload gray");
-    else
-        s = check_hip(c, hipMemcpy2DAsync(c->d_pyr, c->cfg.lv[0].stride, gray, step, c->W, c->H, hipMemcpyHostToDevice, c->stream),
-                      "upload gray");
+    // level 0 of frame 0: of the front end's BRIEF pyramid (tight rows) where it has one, else of the ORB pyramid
+    BriefFront* bf = c->front ? c->front->brief() : nullptr;
+    s = check_hip(c, hipMemcpy2DAsync(bf ? bf->d_pyr : c->d_pyr, bf ? c->W : c->cfg.lv[0].stride, gray, step, c->W, c->H,
+                                      hipMemcpyHostToDevice, c->stream), "upload gray");
     if (s) return s;
     if ((s = run_extract(c, nullptr, nullptr, 1, true))) return s;
     return read_frame(c, 0, kps, nullptr, desc, nullptr, cap, n);

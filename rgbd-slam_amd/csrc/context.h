@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -11,7 +12,7 @@
 #include "rgbd_internal.h"
 
 namespace rgbd {
-struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct SvoWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct AdpWS; struct GfttWS; struct CvorbWS;
+struct RansacWS; struct PnpWS; struct PnpPipe; struct GicpWS; struct LaneWS; struct CloudWS; struct ProjWS; struct BaWS; struct UmWS; struct BowWS; struct BriefFront;
 // the per-batch extraction outputs a step's knn-2 / gather read, as the kernels see them
 struct OutSet {
     int* count = nullptr;
@@ -28,6 +29,19 @@ struct OutBufs {   // one owned set
     DevBuf<float> xyz;
     DevBuf<int4> knn;
     OutSet view() const { return OutSet{count, kps, kun, desc, xyz, knn}; }
+};
+// called by an extraction at its launch points (launch-stream order): 0 before FAST, 1 after FAST,
+// 2 after the quadtree (the pipelined PnP solves use point 1; SVO extractions call points 1 and 2)
+using ExtractHook = std::function<rgbd_status(int at)>;
+inline rgbd_status call_hook(const ExtractHook* hook, int at) { return hook ? (*hook)(at) : RGBD_OK; }
+// an extractor other than the ORBextractor, in rgbd_ctx::front.  Its debug and state entry points are free functions
+// of the file that defines it, which downcasts the slot to its own type.
+struct FrontEnd {
+    virtual ~FrontEnd() = default;
+    virtual rgbd_status alloc(rgbd_ctx* c) = 0;   // after the context's own allocations
+    virtual rgbd_status run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                            const ExtractHook* after_fast) = 0;   // one launch chain, ends with last_B set
+    virtual BriefFront* brief() { return nullptr; }   // the SVO pyramid + BRIEF plumbing, where the extractor uses it
 };
 }  // namespace rgbd
 
@@ -87,10 +101,7 @@ struct rgbd_ctx {
     rgbd::GicpWS* gicp = nullptr;        // gicp_host.cpp
     rgbd::LaneWS* lanes = nullptr;       // device-resident RansacSE3 tracking chain (lanes_host.cpp)
     rgbd::CloudWS* cloud = nullptr;      // keyframe cloud (cloud_host.cpp)
-    rgbd::SvoWS* svo = nullptr;          // SVO + BRIEF extractor (svo_host.cpp); null: ORBextractor
-    rgbd::AdpWS* adaptive = nullptr;     // adaptive FAST + BRIEF extractor (adaptive_host.cpp); takes precedence over svo
-    rgbd::GfttWS* gftt = nullptr;        // Shi-Tomasi GFTT + BRIEF extractor (gftt_host.cpp); a context has at most one of svo / adaptive / gftt
-    rgbd::CvorbWS* cvorb = nullptr;      // OpenCV ORB extractor (cvorb_host.cpp); likewise exclusive
+    std::unique_ptr<rgbd::FrontEnd> front;   // the extractor; null: the ORBextractor
     rgbd::ProjWS* proj = nullptr;        // projection-guided matching (project_host.cpp)
     rgbd::BaWS* pnpba = nullptr;         // motion-only bundle adjustment, PnPSolver (pnpba_host.cpp)
     rgbd::UmWS* umeyama = nullptr;       // Umeyama RANSAC, Ransac (umeyama_host.cpp)
@@ -110,9 +121,6 @@ struct rgbd_ctx {
 };
 
 namespace rgbd {
-// called by an extraction at its launch points (launch-stream order): 0 before FAST, 1 after FAST,
-// 2 after the quadtree (the pipelined PnP solves use point 1; SVO extractions call points 1 and 2)
-using ExtractHook = std::function<rgbd_status(int at)>;
 rgbd_status extract_batch(rgbd_ctx* c, const void* d_bgr, const void* d_depth, int B, const ExtractHook* after_fast);
 // records the elapsed time of the launches between begin and end under `name`
 int timer_begin(rgbd_ctx* c, const char* name, hipStream_t st = nullptr);   // nullptr: the context stream
@@ -157,37 +165,12 @@ void proj_free(rgbd_ctx* c);     // project_host.cpp
 void pnpba_free(rgbd_ctx* c);    // pnpba_host.cpp
 void umeyama_free(rgbd_ctx* c);  // umeyama_host.cpp
 void bow_free(rgbd_ctx* c);      // bow_host.cpp
-// svo_host.cpp: the Extractor(SVO, BRIEF, NORMAL) front end of an rgbd_create_svo context
-rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p);   // before the output allocations
-rgbd_status svo_alloc(rgbd_ctx* c);
-void svo_free(rgbd_ctx* c);
-rgbd_status svo_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                            const ExtractHook* after_fast);
-uint8_t* svo_gray_level(rgbd_ctx* c);   // level 0 of the SVO pyramid (frame 0): the gray upload target
-// adaptive_host.cpp: the Extractor(FAST, BRIEF, ADAPTIVE) front end of an rgbd_create_adaptive context
-rgbd_status adaptive_configure(rgbd_ctx* c, const rgbd_adaptive_params& p);   // validates; before the output allocations
-rgbd_status adaptive_alloc(rgbd_ctx* c);
-void adaptive_free(rgbd_ctx* c);
-rgbd_status adaptive_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                                 const ExtractHook* after_fast);
-uint8_t* adaptive_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
-rgbd_status adaptive_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
-rgbd_status adaptive_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
-// gftt_host.cpp: the Extractor(GFTT, BRIEF, NORMAL) front end of an rgbd_create_gftt context
-rgbd_status gftt_configure(rgbd_ctx* c, const rgbd_gftt_params& p);   // validates; before the output allocations
-rgbd_status gftt_alloc(rgbd_ctx* c);
-void gftt_free(rgbd_ctx* c);
-rgbd_status gftt_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                             const ExtractHook* after_fast);
-uint8_t* gftt_gray_level(rgbd_ctx* c);   // the gray image of frame 0: the gray upload target
-rgbd_status gftt_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs);   // behind rgbd_svo_set / get_brief_pattern
-rgbd_status gftt_get_brief_pattern(rgbd_ctx* c, int8_t* pairs);
-// cvorb_host.cpp: the Extractor(ORB, ORB, NORMAL) front end of an rgbd_create_cvorb context (it runs on the ORB
-// geometry's pyramid, so the gray upload target is the ORBextractor's)
-rgbd_status cvorb_check_params(rgbd_ctx* c, const rgbd_cvorb_params& p);   // the parameter refusals, before the geometry's
-rgbd_status cvorb_configure(rgbd_ctx* c, const rgbd_cvorb_params& p);      // on an accepted geometry; before the output allocations
-rgbd_status cvorb_alloc(rgbd_ctx* c);
-void cvorb_free(rgbd_ctx* c);
-rgbd_status cvorb_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                              const ExtractHook* after_fast);
+// k_pyramid and k_pyr_tail, or k_gray for a one-level pyramid, into c->d_pyr (api.cpp)
+rgbd_status run_orb_pyramid(rgbd_ctx* c, const uint8_t* d_bgr, int B, bool from_gray);
+// the extractors' configure steps: each validates, sets c->front and cfg.kp_cap (which sizes the output arrays)
+rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p);             // svo_host.cpp
+rgbd_status adaptive_configure(rgbd_ctx* c, const rgbd_adaptive_params& p);   // adaptive_host.cpp
+rgbd_status gftt_configure(rgbd_ctx* c, const rgbd_gftt_params& p);           // gftt_host.cpp
+rgbd_status cvorb_check_params(rgbd_ctx* c, const rgbd_cvorb_params& p);      // cvorb_host.cpp: the parameter refusals, before the geometry's
+rgbd_status cvorb_configure(rgbd_ctx* c, const rgbd_cvorb_params& p);         // on an accepted geometry
 }  // namespace rgbd

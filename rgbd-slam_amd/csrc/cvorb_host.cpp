@@ -1,7 +1,7 @@
 // cvorb_host.cpp -- host side of the OpenCV ORB front end (cvorb.hip): Extractor(ORB, ORB, NORMAL), behind the same
 // extraction entry points as the ORBextractor, the SVO, the adaptive and the GFTT front ends.
 //   Extractor::create(ORB)        Features/Extractor.cpp:163-166, 216-218  -> cvorb_configure (CvorbCfg)
-//   Extractor::detectAndCompute   Features/Extractor.cpp:50-61             -> cvorb_run_extract (one launch chain)
+//   Extractor::detectAndCompute   Features/Extractor.cpp:50-61             -> CvorbWS::run (one launch chain)
 //   Frame::undistortKeyPoints + uprojectCamera (Core/Frame.cpp:91-117, 251-281) -> k_undistort
 // The pyramid and the blurred pyramid are the ORB geometry's (geometry.cpp): k_pyramid / k_pyr_tail and the blur
 // blocks of the k_fast grid, launched without FAST segments.
@@ -18,7 +18,7 @@
 
 namespace rgbd {
 
-struct CvorbWS {
+struct CvorbWS : FrontEnd {
     CvorbCfg cfg{};
     DevBuf<uint8_t> d_score;       // [B][frame_pyr_bytes]
     DevBuf<uint32_t> d_cand, d_s1, d_s2;   // [B][L][cand_cap]
@@ -26,11 +26,15 @@ struct CvorbWS {
     DevBuf<int> d_n;               // nfast, n1, n2: [3][B][L], then nstrip [B][L][kCvListStrips]
     DevBuf<uint32_t> d_fsel;       // [B][kp_cap]
     CvorbBufs bufs{};
+
+    rgbd_status alloc(rgbd_ctx* c) override;
+    rgbd_status run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                    const ExtractHook* after_fast) override;
 };
 
 namespace {
 
-CvorbWS* ws(rgbd_ctx* c) { return c->cvorb; }
+CvorbWS* ws(rgbd_ctx* c) { return dynamic_cast<CvorbWS*>(c->front.get()); }   // null: not a cv::ORB context
 
 rgbd_status not_cvorb(rgbd_ctx* c) { return fail(c, RGBD_ERR_ARG, "not a cv::ORB context (rgbd_create_cvorb)"); }
 
@@ -92,84 +96,61 @@ rgbd_status cvorb_configure(rgbd_ctx* c, const rgbd_cvorb_params& p)
     g.N[g.nlevels - 1] = std::max(p.nfeatures - sum, 0);
     for (int v = 0; v < 16; v++) g.umax[v] = C.umax[v];
     CvorbWS* w = new CvorbWS();
-    c->cvorb = w;
+    c->front.reset(w);
     w->cfg = g;
     c->cfg.kp_cap = g.kp_cap;   // the output arrays (kps, desc, xyz, knn) are sized by it
     return RGBD_OK;
 }
 
-rgbd_status cvorb_alloc(rgbd_ctx* c)
+rgbd_status CvorbWS::alloc(rgbd_ctx* c)
 {
-    CvorbWS* w = ws(c);
-    const CvorbCfg& g = w->cfg;
+    const CvorbCfg& g = cfg;
     const size_t B = (size_t)c->maxB, BL = B * g.nlevels, lists = BL * g.cand_cap;
-    rgbd_status s = check_hip(c, w->d_score.alloc(B * g.frame_pyr_bytes + 64), "cv::ORB score maps");
-    if (!s) s = check_hip(c, w->d_cand.alloc(lists), "cv::ORB corners");
-    if (!s) s = check_hip(c, w->d_s1.alloc(lists), "cv::ORB first selection");
-    if (!s) s = check_hip(c, w->d_h1.alloc(lists), "cv::ORB Harris responses");
-    if (!s) s = check_hip(c, w->d_s2.alloc(lists), "cv::ORB second selection");
-    if (!s) s = check_hip(c, w->d_h2.alloc(lists), "cv::ORB kept responses");
-    if (!s) s = check_hip(c, w->d_n.alloc((3 + kCvListStrips) * BL), "cv::ORB counts");
-    if (!s) s = check_hip(c, w->d_fsel.alloc(B * g.kp_cap), "cv::ORB keypoint positions");
-    if (!s) s = check_hip(c, hipMemset(w->d_score, 0, B * g.frame_pyr_bytes + 64), "memset score maps");
-    if (!s) s = check_hip(c, hipMemset(w->d_n, 0, (3 + kCvListStrips) * BL * sizeof(int)), "memset cv::ORB counts");
+    rgbd_status s = check_hip(c, d_score.alloc(B * g.frame_pyr_bytes + 64), "cv::ORB score maps");
+    if (!s) s = check_hip(c, d_cand.alloc(lists), "cv::ORB corners");
+    if (!s) s = check_hip(c, d_s1.alloc(lists), "cv::ORB first selection");
+    if (!s) s = check_hip(c, d_h1.alloc(lists), "cv::ORB Harris responses");
+    if (!s) s = check_hip(c, d_s2.alloc(lists), "cv::ORB second selection");
+    if (!s) s = check_hip(c, d_h2.alloc(lists), "cv::ORB kept responses");
+    if (!s) s = check_hip(c, d_n.alloc((3 + kCvListStrips) * BL), "cv::ORB counts");
+    if (!s) s = check_hip(c, d_fsel.alloc(B * g.kp_cap), "cv::ORB keypoint positions");
+    if (!s) s = check_hip(c, hipMemset(d_score, 0, B * g.frame_pyr_bytes + 64), "memset score maps");
+    if (!s) s = check_hip(c, hipMemset(d_n, 0, (3 + kCvListStrips) * BL * sizeof(int)), "memset cv::ORB counts");
     if (s) return s;
-    w->bufs = CvorbBufs{w->d_score, w->d_cand, w->d_n, w->d_n + 3 * BL, w->d_s1, w->d_h1, w->d_n + BL, w->d_s2, w->d_h2, w->d_n + 2 * BL, w->d_fsel};
+    bufs = CvorbBufs{d_score, d_cand, d_n, d_n + 3 * BL, d_s1, d_h1, d_n + BL, d_s2, d_h2, d_n + 2 * BL, d_fsel};
     return RGBD_OK;
 }
 
-void cvorb_free(rgbd_ctx* c)
+rgbd_status CvorbWS::run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                         const ExtractHook* after_fast)
 {
-    delete c->cvorb;
-    c->cvorb = nullptr;
-}
-
-rgbd_status cvorb_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                              const ExtractHook* after_fast)
-{
-    CvorbWS* w = ws(c);
-    const CvorbCfg& g = w->cfg;
+    const CvorbCfg& g = cfg;
     const ExtractCfg& C = c->cfg;
     const hipStream_t st = c->stream;
-    int tk;
-    if (C.nlevels > 1) {
-        tk = timer_begin(c, "k_pyramid");
-        RGBD_TRY(c, launch_pyramid(c->d_pyr, from_gray ? nullptr : d_bgr, c->d_rsy, c->d_qx, c->d_cfg, C.pyr_lds + C.pyr_rsy_lds, B, st), "pyramid");
-        timer_end(c, tk);
-        if (C.pyr_top < C.nlevels) {
-            tk = timer_begin(c, "k_pyr_tail");
-            RGBD_TRY(c, launch_pyr_tail(c->d_pyr, c->d_rsy, c->d_qx, c->d_cfg, B, st), "pyramid tail");
-            timer_end(c, tk);
-        }
-    } else if (!from_gray) {
-        tk = timer_begin(c, "k_gray");
-        RGBD_TRY(c, launch_gray(d_bgr, c->d_pyr, C.W, C.H, C.frame_pyr_bytes, B, st), "gray");
-        timer_end(c, tk);
-    }
-    auto hook = [&](int at) -> rgbd_status { return after_fast ? (*after_fast)(at) : RGBD_OK; };
-    rgbd_status hs;
-    if ((hs = hook(0))) return hs;
+    rgbd_status hs = run_orb_pyramid(c, d_bgr, B, from_gray);
+    if (hs) return hs;
+    if ((hs = call_hook(after_fast, 0))) return hs;
     // the k_fast grid's blur blocks alone (no FAST segments): the blurred pyramid
-    tk = timer_begin(c, "k_fast(blur)");
+    int tk = timer_begin(c, "k_fast(blur)");
     RGBD_TRY(c, launch_fast(c->d_pyr, c->d_cells, c->d_segs, 0, c->d_cfg, c->d_cellc, c->d_slots, B, st, c->d_blur,
                             C.blur_t0[kMaxLevels] + C.blur_e0[kMaxLevels], c->d_blur_tab, C.blur_m0[kMaxLevels]), "fast (blur blocks)");
     timer_end(c, tk);
     tk = timer_begin(c, "k_cvorb_score");
-    RGBD_TRY(c, launch_cvorb_score(c->d_pyr, g, w->bufs, B, st), "cvorb_score");
+    RGBD_TRY(c, launch_cvorb_score(c->d_pyr, g, bufs, B, st), "cvorb_score");
     timer_end(c, tk);
     tk = timer_begin(c, "k_cvorb_list");
-    RGBD_TRY(c, launch_cvorb_list(g, w->bufs, c->d_err, B, st), "cvorb_list");
+    RGBD_TRY(c, launch_cvorb_list(g, bufs, c->d_err, B, st), "cvorb_list");
     timer_end(c, tk);
-    if ((hs = hook(1))) return hs;   // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
+    if ((hs = call_hook(after_fast, 1))) return hs;   // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
     tk = timer_begin(c, "k_cvorb_select");
-    RGBD_TRY(c, launch_cvorb_select(c->d_pyr, g, w->bufs, B, st), "cvorb_select");
+    RGBD_TRY(c, launch_cvorb_select(c->d_pyr, g, bufs, B, st), "cvorb_select");
     timer_end(c, tk);
     tk = timer_begin(c, "k_cvorb_frame");
-    RGBD_TRY(c, launch_cvorb_frame(g, w->bufs, c->out.count, c->out.kps, c->d_err, B, st), "cvorb_frame");
+    RGBD_TRY(c, launch_cvorb_frame(g, bufs, c->out.count, c->out.kps, c->d_err, B, st), "cvorb_frame");
     timer_end(c, tk);
-    if ((hs = hook(2))) return hs;
+    if ((hs = call_hook(after_fast, 2))) return hs;
     tk = timer_begin(c, "k_cvorb_describe");
-    RGBD_TRY(c, launch_cvorb_describe(c->d_pyr, c->d_blur, g, w->bufs, c->out.count, c->out.kps, c->out.desc, B, st), "cvorb_describe");
+    RGBD_TRY(c, launch_cvorb_describe(c->d_pyr, c->d_blur, g, bufs, c->out.count, c->out.kps, c->out.desc, B, st), "cvorb_describe");
     timer_end(c, tk);
     tk = timer_begin(c, "k_undistort");
     RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, g.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
@@ -188,8 +169,8 @@ rgbd_status rgbd_cvorb_debug_level(rgbd_ctx* c, int32_t b, int32_t level, int32_
                                    int32_t* n)
 {
     if (!c || !n) return RGBD_ERR_ARG;
-    if (!c->cvorb) return not_cvorb(c);
     CvorbWS* w = ws(c);
+    if (!w) return not_cvorb(c);
     const CvorbCfg& g = w->cfg;
     if (b < 0 || b >= c->last_B) return fail(c, RGBD_ERR_ARG, "cv::ORB: frame index outside the last batch");
     if (level < 0 || level >= g.nlevels || stage < 0 || stage > 3 || cap < 0)

@@ -1,7 +1,7 @@
 // gftt_host.cpp -- host side of the Shi-Tomasi GFTT + BRIEF front end (gftt.hip): Extractor(GFTT, BRIEF, NORMAL),
 // behind the same extraction entry points as the ORBextractor, the SVO and the adaptive front ends.
 //   Extractor::create(GFTT)       Features/Extractor.cpp:178-181  -> gftt_configure (GfttCfg)
-//   Extractor::detectAndCompute   Features/Extractor.cpp:50-61    -> gftt_run_extract (one launch chain)
+//   Extractor::detectAndCompute   Features/Extractor.cpp:50-61    -> GfttWS::run (one launch chain)
 //   Frame::undistortKeyPoints + uprojectCamera (Core/Frame.cpp:91-117, 251-281) -> k_undistort
 #include <hip/hip_runtime.h>
 
@@ -11,47 +11,33 @@
 #include <unordered_map>
 #include <vector>
 
-#include "context.h"
+#include "brief_front.h"
 #include "gftt_dev.h"
 #include "launch.h"
-#include "svo_dev.h"
 
 namespace rgbd {
 
-struct GfttWS {
+struct GfttWS : FrontEnd {
     GfttCfg cfg{};
-    SvoCfg pyr{};                  // k_svo_pyramid (one level: gray + box sums) and k_svo_brief
-    DevBuf<uint8_t> d_gray;        // [B][frame_bytes]
-    DevBuf<uint16_t> d_box;        // [B][H][W]
+    BriefFront bf;                 // one level: gray + box sums
     DevBuf<uint32_t> d_maxkey;     // [B]
     DevBuf<uint64_t> d_keys;       // [B][cand_cap]
     DevBuf<int> d_ncand;           // [B]
     DevBuf<uint64_t> d_corners;    // [B][nfeatures]
     DevBuf<int> d_ncorner, d_ranks;   // [B]
-    DevBuf<uint32_t> d_pat;
     DevBuf<float> d_eig;           // rgbd_gftt_debug_eig staging, [H][W]
     DevBuf<uint64_t> d_sel_keys, d_sel_out;   // rgbd_gftt_select staging
     DevBuf<int> d_sel_n;           // its ncorner, ranks
-    int8_t pattern[256 * 4];
+
+    rgbd_status alloc(rgbd_ctx* c) override;
+    rgbd_status run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                    const ExtractHook* after_fast) override;
+    BriefFront* brief() override { return &bf; }
 };
 
 namespace {
 
-const int8_t kDefaultBrief[256 * 4] = {
-#include "brief_pattern.inc"
-};
-
-GfttWS* ws(rgbd_ctx* c) { return c->gftt; }
-
-rgbd_status upload_pattern(rgbd_ctx* c, GfttWS* w)
-{
-    uint32_t packed[256];
-    for (int t = 0; t < 256; t++) {
-        const uint8_t* q = reinterpret_cast<const uint8_t*>(w->pattern + 4 * t);
-        packed[t] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
-    return check_hip(c, hipMemcpyAsync(w->d_pat, packed, sizeof(packed), hipMemcpyHostToDevice, c->stream), "brief pattern");
-}
+GfttWS* ws(rgbd_ctx* c) { return dynamic_cast<GfttWS*>(c->front.get()); }   // null: not a GFTT context
 
 rgbd_status not_gftt(rgbd_ctx* c) { return fail(c, RGBD_ERR_ARG, "not a GFTT context (rgbd_create_gftt)"); }
 
@@ -76,104 +62,55 @@ rgbd_status gftt_configure(rgbd_ctx* c, const rgbd_gftt_params& p)
     g.cand_cap = p.cand_cap > 0 ? p.cand_cap : kGfttDefaultCandCap;
     g.chunk = gftt_default_chunk(p.nfeatures);
     g.dist_lim = dist_limit(p.min_distance);
-    g.border = 48 / 2 + 9 / 2;                            // BriefDescriptorExtractorImpl PATCH_SIZE, KERNEL_SIZE
+    g.border = kBriefBorder;
     g.kp_cap = p.nfeatures;
     g.quality_level = p.quality_level;
     GfttWS* w = new GfttWS();
-    c->gftt = w;
+    c->front.reset(w);
     w->cfg = g;
-    SvoCfg& s = w->pyr;
-    s.W = c->W;
-    s.H = c->H;
-    s.nlevels = 1;
-    s.lw[0] = c->W;
-    s.lh[0] = c->H;
-    s.loff[0] = 0;
-    s.frame_bytes = (c->W * c->H + 63) & ~63;
-    s.kp_cap = g.kp_cap;
-    s.border = g.border;
-    std::memcpy(w->pattern, kDefaultBrief, sizeof(kDefaultBrief));
+    w->bf.one_level(c->W, c->H, g.kp_cap);
     c->cfg.kp_cap = g.kp_cap;   // the output arrays (kps, desc, xyz, knn) are sized by it
     return RGBD_OK;
 }
 
-rgbd_status gftt_alloc(rgbd_ctx* c)
+rgbd_status GfttWS::alloc(rgbd_ctx* c)
 {
-    GfttWS* w = ws(c);
-    const GfttCfg& g = w->cfg;
+    const GfttCfg& g = cfg;
     const size_t B = (size_t)c->maxB;
-    rgbd_status s = check_hip(c, w->d_gray.alloc(B * w->pyr.frame_bytes + 64), "gftt gray");
-    if (!s) s = check_hip(c, w->d_box.alloc(B * g.W * g.H), "gftt box");
-    if (!s) s = check_hip(c, w->d_maxkey.alloc(B), "gftt maxima");
-    if (!s) s = check_hip(c, w->d_keys.alloc(B * g.cand_cap), "gftt candidates");
-    if (!s) s = check_hip(c, w->d_ncand.alloc(B), "gftt candidate counts");
-    if (!s) s = check_hip(c, w->d_corners.alloc(B * g.nfeatures), "gftt corners");
-    if (!s) s = check_hip(c, w->d_ncorner.alloc(B), "gftt corner counts");
-    if (!s) s = check_hip(c, w->d_ranks.alloc(B), "gftt ranks");
-    if (!s) s = check_hip(c, w->d_pat.alloc(256), "gftt pattern");
-    if (s) return s;
-    s = upload_pattern(c, w);
+    rgbd_status s = bf.alloc(c, "gftt", "gray");
+    if (!s) s = check_hip(c, d_maxkey.alloc(B), "gftt maxima");
+    if (!s) s = check_hip(c, d_keys.alloc(B * g.cand_cap), "gftt candidates");
+    if (!s) s = check_hip(c, d_ncand.alloc(B), "gftt candidate counts");
+    if (!s) s = check_hip(c, d_corners.alloc(B * g.nfeatures), "gftt corners");
+    if (!s) s = check_hip(c, d_ncorner.alloc(B), "gftt corner counts");
+    if (!s) s = check_hip(c, d_ranks.alloc(B), "gftt ranks");
     if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "sync");
     return s;
 }
 
-void gftt_free(rgbd_ctx* c)
+rgbd_status GfttWS::run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                        const ExtractHook* after_fast)
 {
-    delete c->gftt;
-    c->gftt = nullptr;
-}
-
-uint8_t* gftt_gray_level(rgbd_ctx* c) { return ws(c)->d_gray; }
-
-rgbd_status gftt_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                             const ExtractHook* after_fast)
-{
-    GfttWS* w = ws(c);
-    const GfttCfg& g = w->cfg;
+    const GfttCfg& g = cfg;
     const hipStream_t st = c->stream;
-    const size_t fb = (size_t)w->pyr.frame_bytes;
-    rgbd_status s = check_hip(c, hipMemsetAsync(w->d_maxkey, 0, 4 * (size_t)B, st), "clear gftt maxima");
-    if (!s) s = check_hip(c, hipMemsetAsync(w->d_ncand, 0, 4 * (size_t)B, st), "clear gftt counts");
+    const size_t fb = (size_t)bf.cfg.frame_bytes;
+    rgbd_status s = check_hip(c, hipMemsetAsync(d_maxkey, 0, 4 * (size_t)B, st), "clear gftt maxima");
+    if (!s) s = check_hip(c, hipMemsetAsync(d_ncand, 0, 4 * (size_t)B, st), "clear gftt counts");
+    if (!s) s = bf.run_pyramid(c, d_bgr, B, from_gray);
     if (s) return s;
-    int tk = timer_begin(c, "k_svo_pyramid");
-    RGBD_TRY(c, launch_svo_pyramid(from_gray ? nullptr : d_bgr, w->d_gray, w->d_box, w->pyr, B, st), "svo_pyramid");
-    timer_end(c, tk);
-    tk = timer_begin(c, "k_gftt_max");
-    RGBD_TRY(c, launch_gftt_max(w->d_gray, fb, g, w->d_maxkey, B, st), "gftt_max");
+    int tk = timer_begin(c, "k_gftt_max");
+    RGBD_TRY(c, launch_gftt_max(bf.d_pyr, fb, g, d_maxkey, B, st), "gftt_max");
     timer_end(c, tk);
     tk = timer_begin(c, "k_gftt_cand");
-    RGBD_TRY(c, launch_gftt_cand(w->d_gray, fb, g, w->d_maxkey, w->d_keys, w->d_ncand, c->d_err, B, st), "gftt_cand");
+    RGBD_TRY(c, launch_gftt_cand(bf.d_pyr, fb, g, d_maxkey, d_keys, d_ncand, c->d_err, B, st), "gftt_cand");
     timer_end(c, tk);
-    if (after_fast) {   // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
-        rgbd_status hs = (*after_fast)(1);
-        if (!hs) hs = (*after_fast)(2);
-        if (hs) return hs;
-    }
+    // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
+    if ((s = call_hook(after_fast, 1)) || (s = call_hook(after_fast, 2))) return s;
     tk = timer_begin(c, "k_gftt_select");
-    RGBD_TRY(c, launch_gftt_select(w->d_keys, w->d_ncand, 0, g, w->d_corners, w->d_ncorner, w->d_ranks, c->out.count, c->out.kps,
-                                   B, st), "gftt_select");
+    RGBD_TRY(c, launch_gftt_select(d_keys, d_ncand, 0, g, d_corners, d_ncorner, d_ranks, c->out.count, c->out.kps, B, st),
+             "gftt_select");
     timer_end(c, tk);
-    tk = timer_begin(c, "k_svo_brief");
-    RGBD_TRY(c, launch_svo_brief(w->d_box, c->out.count, c->out.kps, w->d_pat, w->pyr, c->out.desc, B, st), "svo_brief");
-    timer_end(c, tk);
-    tk = timer_begin(c, "k_undistort");
-    RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, g.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
-    timer_end(c, tk);
-    c->last_B = B;
-    return RGBD_OK;
-}
-
-rgbd_status gftt_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs)
-{
-    std::memcpy(ws(c)->pattern, pairs, 1024);
-    rgbd_status s = upload_pattern(c, ws(c));
-    return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "sync");
-}
-
-rgbd_status gftt_get_brief_pattern(rgbd_ctx* c, int8_t* pairs)
-{
-    std::memcpy(pairs, ws(c)->pattern, 1024);
-    return RGBD_OK;
+    return bf.run_describe(c, d_depth, B);
 }
 
 }  // namespace rgbd
@@ -185,7 +122,7 @@ extern "C" {
 rgbd_status rgbd_gftt_debug_eig(rgbd_ctx* c, int32_t b, float* out)
 {
     if (!c || !out) return RGBD_ERR_ARG;
-    if (!c->gftt) return not_gftt(c);
+    if (!ws(c)) return not_gftt(c);
     if (b < 0 || b >= c->last_B) return fail(c, RGBD_ERR_ARG, "gftt: frame index outside the last batch");
     GfttWS* w = ws(c);
     const GfttCfg& g = w->cfg;
@@ -193,7 +130,7 @@ rgbd_status rgbd_gftt_debug_eig(rgbd_ctx* c, int32_t b, float* out)
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (!s && !w->d_eig) s = check_hip(c, w->d_eig.alloc(px), "gftt map");
     if (s) return s;
-    RGBD_TRY(c, launch_gftt_eig(w->d_gray + (size_t)b * w->pyr.frame_bytes, g, w->d_eig, c->stream), "gftt_eig");
+    RGBD_TRY(c, launch_gftt_eig(w->bf.d_pyr + (size_t)b * w->bf.cfg.frame_bytes, g, w->d_eig, c->stream), "gftt_eig");
     s = check_hip(c, hipMemcpyAsync(out, w->d_eig, px * 4, hipMemcpyDeviceToHost, c->stream), "read gftt map");
     return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "sync");
 }
@@ -202,7 +139,7 @@ rgbd_status rgbd_gftt_debug_corners(rgbd_ctx* c, int32_t b, uint32_t* max_bits, 
                                     int32_t cap, int32_t* n)
 {
     if (!c) return RGBD_ERR_ARG;
-    if (!c->gftt) return not_gftt(c);
+    if (!ws(c)) return not_gftt(c);
     if (b < 0 || b >= c->last_B) return fail(c, RGBD_ERR_ARG, "gftt: frame index outside the last batch");
     if (cap < 0) return fail(c, RGBD_ERR_ARG, "gftt: negative output capacity");
     GfttWS* w = ws(c);
@@ -243,7 +180,7 @@ rgbd_status rgbd_gftt_debug_corners(rgbd_ctx* c, int32_t b, uint32_t* max_bits, 
 rgbd_status rgbd_gftt_debug_ranks(rgbd_ctx* c, int32_t b, int32_t* ranks)
 {
     if (!c || !ranks) return RGBD_ERR_ARG;
-    if (!c->gftt) return not_gftt(c);
+    if (!ws(c)) return not_gftt(c);
     if (b < 0 || b >= c->last_B) return fail(c, RGBD_ERR_ARG, "gftt: frame index outside the last batch");
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (!s) s = check_hip(c, hipMemcpyAsync(ranks, ws(c)->d_ranks + b, 4, hipMemcpyDeviceToHost, c->stream), "read gftt ranks");
@@ -254,7 +191,7 @@ rgbd_status rgbd_gftt_select(rgbd_ctx* c, const int32_t* xy, const float* val, i
                              double min_distance, int32_t max_corners, int32_t chunk, int32_t* out_idx, int32_t* m)
 {
     if (!c || !m || n < 0 || (n > 0 && (!xy || !val)) || !out_idx) return RGBD_ERR_ARG;
-    if (!c->gftt) return not_gftt(c);
+    if (!ws(c)) return not_gftt(c);
     *m = 0;
     if (W < 1 || H < 1 || W > 2047 || H > 2047 || n > kGfttMaxCandCap || max_corners < 1 || max_corners > kGfttMaxCorners ||
         chunk < 0 || chunk > kGfttMaxChunk || !std::isfinite(min_distance) || min_distance < 0.0 || min_distance > 64.0)

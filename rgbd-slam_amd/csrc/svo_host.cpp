@@ -1,7 +1,7 @@
 // svo_host.cpp -- host side of the SVO + BRIEF front end (svo.hip): Extractor(SVO, BRIEF, NORMAL), the
 // reference's default (main.cpp:31), behind the same extraction entry points as the ORBextractor.
 //   Extractor::createDetector SVO   Features/Extractor.cpp:162-165  -> svo_configure (SvoCfg, tile table)
-//   Extractor::detectAndCompute     Features/Extractor.cpp:50-61    -> svo_run_extract (one launch chain)
+//   Extractor::detectAndCompute     Features/Extractor.cpp:50-61    -> SvoWS::run (one launch chain)
 //   Frame::undistortKeyPoints + uprojectCamera (Core/Frame.cpp:91-117, 251-281) -> k_undistort
 #include <hip/hip_runtime.h>
 
@@ -10,44 +10,30 @@
 #include <cstring>
 #include <vector>
 
-#include "context.h"
+#include "brief_front.h"
 #include "launch.h"
-#include "svo_dev.h"
 
 namespace rgbd {
 
-struct SvoWS {
-    SvoCfg cfg{};
+struct SvoWS : FrontEnd {
+    BriefFront bf;             // its cfg is the SVO configuration, its d_pyr the SVO pyramid
     std::vector<SvoTile> tiles;
     DevBuf<SvoTile> d_tiles;
-    DevBuf<uint8_t> d_pyr;
     DevBuf<unsigned long long> d_cells;
-    DevBuf<uint16_t> d_box;
     DevBuf<uint2> d_cand;
     DevBuf<int> d_ncand;
-    DevBuf<uint32_t> d_pat;
     DevBuf<float> d_rt_resp;   // rgbd_svo_retain_best staging
     DevBuf<int> d_rt_order;
-    int8_t pattern[256 * 4];
+
+    rgbd_status alloc(rgbd_ctx* c) override;
+    rgbd_status run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                    const ExtractHook* after_fast) override;
+    BriefFront* brief() override { return &bf; }
 };
 
 namespace {
 
-const int8_t kDefaultBrief[256 * 4] = {
-#include "brief_pattern.inc"
-};
-
-SvoWS* ws(rgbd_ctx* c) { return c->svo; }
-
-rgbd_status upload_pattern(rgbd_ctx* c, SvoWS* w)
-{
-    uint32_t packed[256];
-    for (int t = 0; t < 256; t++) {
-        const uint8_t* q = reinterpret_cast<const uint8_t*>(w->pattern + 4 * t);
-        packed[t] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
-    }
-    return check_hip(c, hipMemcpyAsync(w->d_pat, packed, sizeof(packed), hipMemcpyHostToDevice, c->stream), "brief pattern");
-}
+SvoWS* ws(rgbd_ctx* c) { return dynamic_cast<SvoWS*>(c->front.get()); }   // null: not an SVO context
 
 }  // namespace
 
@@ -60,8 +46,8 @@ rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p)
     if (c->W < 1 || c->H < 1 || c->W > 2047 || c->H > 2047)
         return fail(c, RGBD_ERR_UNSUPPORTED, "SVO: image sides 1..2047");
     SvoWS* w = new SvoWS();
-    c->svo = w;
-    SvoCfg& g = w->cfg;
+    c->front.reset(w);
+    SvoCfg& g = w->bf.cfg;
     g.W = c->W;
     g.H = c->H;
     g.nlevels = p.nlevels;
@@ -85,79 +71,53 @@ rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p)
     g.nfeatures = p.nfeatures;
     // retainBest keeps nfeatures + every tie of the boundary response (more fail loudly, RGBD_ERR_CAPACITY)
     g.kp_cap = std::min(g.ncells, p.max_keypoints > 0 ? p.max_keypoints : p.nfeatures + 64);
-    g.border = 48 / 2 + 9 / 2;                            // BriefDescriptorExtractorImpl PATCH_SIZE, KERNEL_SIZE
+    g.border = kBriefBorder;
     for (int l = 0; l < p.nlevels; l++) {   // FAST-10 tiles of 64 x 32 over the detector's domain
         if (g.lw[l] < 7 || g.lh[l] < 7) continue;
         for (int y = 0; y < g.lh[l]; y += 32)
             for (int x = 0; x < g.lw[l]; x += 64) w->tiles.push_back(SvoTile{(int16_t)l, (int16_t)x, (int16_t)y, 0});
     }
-    std::memcpy(w->pattern, kDefaultBrief, sizeof(kDefaultBrief));
     c->cfg.kp_cap = g.kp_cap;   // the output arrays (kps, desc, xyz, knn) are sized by it
     return RGBD_OK;
 }
 
-rgbd_status svo_alloc(rgbd_ctx* c)
+rgbd_status SvoWS::alloc(rgbd_ctx* c)
 {
-    SvoWS* w = ws(c);
-    const SvoCfg& g = w->cfg;
+    const SvoCfg& g = bf.cfg;
     const size_t B = (size_t)c->maxB;
-    rgbd_status s = check_hip(c, w->d_tiles.alloc(w->tiles.size()), "svo tiles");
-    if (!s) s = check_hip(c, w->d_pyr.alloc(B * g.frame_bytes + 64), "svo pyramid");
-    if (!s) s = check_hip(c, w->d_cells.alloc(B * g.ncells), "svo cells");
-    if (!s) s = check_hip(c, w->d_box.alloc(B * g.W * g.H), "svo box");
-    if (!s) s = check_hip(c, w->d_cand.alloc(B * g.ncells), "svo candidates");
-    if (!s) s = check_hip(c, w->d_ncand.alloc(B), "svo candidate counts");
-    if (!s) s = check_hip(c, w->d_pat.alloc(256), "svo pattern");
+    rgbd_status s = check_hip(c, d_tiles.alloc(tiles.size()), "svo tiles");
+    if (!s) s = bf.alloc(c, "svo", "pyramid");
+    if (!s) s = check_hip(c, d_cells.alloc(B * g.ncells), "svo cells");
+    if (!s) s = check_hip(c, d_cand.alloc(B * g.ncells), "svo candidates");
+    if (!s) s = check_hip(c, d_ncand.alloc(B), "svo candidate counts");
     if (s) return s;
-    if (!w->tiles.empty())
-        s = check_hip(c, hipMemcpy(w->d_tiles, w->tiles.data(), w->tiles.size() * sizeof(SvoTile), hipMemcpyHostToDevice),
-                      "svo tiles up");
-    if (!s) s = check_hip(c, hipMemset(w->d_cells, 0, B * g.ncells * 8), "svo cells zero");
-    if (!s) s = check_hip(c, hipMemset(w->d_ncand, 0, B * 4), "svo ncand zero");
-    if (!s) s = upload_pattern(c, w);
+    if (!tiles.empty())
+        s = check_hip(c, hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(SvoTile), hipMemcpyHostToDevice), "svo tiles up");
+    if (!s) s = check_hip(c, hipMemset(d_cells, 0, B * g.ncells * 8), "svo cells zero");
+    if (!s) s = check_hip(c, hipMemset(d_ncand, 0, B * 4), "svo ncand zero");
     if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "sync");
     return s;
 }
 
-void svo_free(rgbd_ctx* c)
+rgbd_status SvoWS::run(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
+                       const ExtractHook* after_fast)
 {
-    delete c->svo;
-    c->svo = nullptr;
-}
-
-uint8_t* svo_gray_level(rgbd_ctx* c) { return ws(c)->d_pyr; }
-
-rgbd_status svo_run_extract(rgbd_ctx* c, const uint8_t* d_bgr, const uint16_t* d_depth, int B, bool from_gray,
-                            const ExtractHook* after_fast)
-{
-    SvoWS* w = ws(c);
-    const SvoCfg& g = w->cfg;
+    const SvoCfg& g = bf.cfg;
     const hipStream_t st = c->stream;
-    int tk = timer_begin(c, "k_svo_pyramid");
-    RGBD_TRY(c, launch_svo_pyramid(from_gray ? nullptr : d_bgr, w->d_pyr, w->d_box, g, B, st), "svo_pyramid");
+    rgbd_status s = bf.run_pyramid(c, d_bgr, B, from_gray);
+    if (s) return s;
+    int tk = timer_begin(c, "k_svo_detect");
+    RGBD_TRY(c, launch_svo_detect(bf.d_pyr, d_tiles, (int)tiles.size(), g, d_cells, B, st), "svo_detect");
     timer_end(c, tk);
-    tk = timer_begin(c, "k_svo_detect");
-    RGBD_TRY(c, launch_svo_detect(w->d_pyr, w->d_tiles, (int)w->tiles.size(), g, w->d_cells, B, st), "svo_detect");
-    timer_end(c, tk);
-    if (after_fast) {   // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
-        rgbd_status hs = (*after_fast)(1);
-        if (!hs) hs = (*after_fast)(2);
-        if (hs) return hs;
-    }
+    // e.g. the deferred PnPRansac solves of earlier pipelined steps (pnp_host.cpp)
+    if ((s = call_hook(after_fast, 1)) || (s = call_hook(after_fast, 2))) return s;
     tk = timer_begin(c, "k_svo_select");
-    RGBD_TRY(c, launch_svo_select(w->d_cells, g, w->d_cand, w->d_ncand, c->out.count, c->out.kps, c->d_err, B, st), "svo_select");
+    RGBD_TRY(c, launch_svo_select(d_cells, g, d_cand, d_ncand, c->out.count, c->out.kps, c->d_err, B, st), "svo_select");
     timer_end(c, tk);
 #ifdef RGBD_PNP_PROFILE
     svo_prof_dump(st);
 #endif
-    tk = timer_begin(c, "k_svo_brief");
-    RGBD_TRY(c, launch_svo_brief(w->d_box, c->out.count, c->out.kps, w->d_pat, g, c->out.desc, B, st), "svo_brief");
-    timer_end(c, tk);
-    tk = timer_begin(c, "k_undistort");
-    RGBD_TRY(c, launch_undistort(d_depth, c->out.count, c->d_cfg, g.kp_cap, c->out.kps, c->out.kun, c->out.xyz, B, st), "undistort");
-    timer_end(c, tk);
-    c->last_B = B;
-    return RGBD_OK;
+    return bf.run_describe(c, d_depth, B);
 }
 
 }  // namespace rgbd
@@ -166,40 +126,13 @@ using namespace rgbd;
 
 extern "C" {
 
-rgbd_status rgbd_svo_set_brief_pattern(rgbd_ctx* c, const int8_t* pairs)
-{
-    if (!c || !pairs) return RGBD_ERR_ARG;
-    if (!c->svo && !c->adaptive && !c->gftt)
-        return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive or GFTT context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt)");
-    for (int i = 0; i < 1024; i++)
-        if (pairs[i] < -24 || pairs[i] > 24) return fail(c, RGBD_ERR_ARG, "BRIEF offsets must lie in [-24, 24]");
-    rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
-    if (s) return s;
-    if (c->adaptive) return adaptive_set_brief_pattern(c, pairs);
-    if (c->gftt) return gftt_set_brief_pattern(c, pairs);
-    std::memcpy(ws(c)->pattern, pairs, 1024);
-    if ((s = upload_pattern(c, ws(c)))) return s;
-    return check_hip(c, hipStreamSynchronize(c->stream), "sync");
-}
-
-rgbd_status rgbd_svo_get_brief_pattern(rgbd_ctx* c, int8_t* pairs)
-{
-    if (!c || !pairs) return RGBD_ERR_ARG;
-    if (c->adaptive) return adaptive_get_brief_pattern(c, pairs);
-    if (c->gftt) return gftt_get_brief_pattern(c, pairs);
-    if (!c->svo)
-        return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive or GFTT context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt)");
-    std::memcpy(pairs, ws(c)->pattern, 1024);
-    return RGBD_OK;
-}
-
 rgbd_status rgbd_svo_debug_level(rgbd_ctx* c, int32_t b, int32_t level, uint8_t* out)
 {
-    if (!c || !out || !c->svo || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
-    SvoWS* w = ws(c);
-    const SvoCfg& g = w->cfg;
+    SvoWS* w = c ? ws(c) : nullptr;
+    if (!w || !out || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
+    const SvoCfg& g = w->bf.cfg;
     if (level < 0 || level >= g.nlevels) return RGBD_ERR_ARG;
-    rgbd_status s = check_hip(c, hipMemcpyAsync(out, w->d_pyr + (size_t)b * g.frame_bytes + g.loff[level],
+    rgbd_status s = check_hip(c, hipMemcpyAsync(out, w->bf.d_pyr + (size_t)b * g.frame_bytes + g.loff[level],
                                                 (size_t)g.lw[level] * g.lh[level], hipMemcpyDeviceToHost, c->stream),
                               "read level");
     return s ? s : check_hip(c, hipStreamSynchronize(c->stream), "sync");
@@ -207,9 +140,9 @@ rgbd_status rgbd_svo_debug_level(rgbd_ctx* c, int32_t b, int32_t level, uint8_t*
 
 rgbd_status rgbd_svo_debug_grid(rgbd_ctx* c, int32_t b, int32_t* xyl, float* resp, int32_t cap, int32_t* n)
 {
-    if (!c || !n || !c->svo || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
-    SvoWS* w = ws(c);
-    const SvoCfg& g = w->cfg;
+    SvoWS* w = c ? ws(c) : nullptr;
+    if (!w || !n || b < 0 || b >= c->last_B) return RGBD_ERR_ARG;
+    const SvoCfg& g = w->bf.cfg;
     int cnt = 0;
     rgbd_status s = check_hip(c, hipMemcpyAsync(&cnt, w->d_ncand + b, 4, hipMemcpyDeviceToHost, c->stream), "read ncand");
     if (!s) s = check_hip(c, hipStreamSynchronize(c->stream), "sync");
@@ -240,11 +173,11 @@ rgbd_status rgbd_svo_retain_best(rgbd_ctx* c, const float* resp, int32_t n, int3
                                  int32_t* order, int32_t* m)
 {
     if (!c || !order || !m || n < 0 || (n > 0 && !resp)) return RGBD_ERR_ARG;
-    if (!c->svo) return fail(c, RGBD_ERR_ARG, "not an SVO context (rgbd_create_svo)");
+    SvoWS* w = ws(c);
+    if (!w) return fail(c, RGBD_ERR_ARG, "not an SVO context (rgbd_create_svo)");
     if (n > kSvoSelThreads * kSvoSelMaxE) return fail(c, RGBD_ERR_UNSUPPORTED, "retainBest: n <= 12288");
     rgbd_status s = check_hip(c, hipSetDevice(c->device), "hipSetDevice");
     if (s) return s;
-    SvoWS* w = ws(c);
     if (!w->d_rt_order) {   // the one allocated last
         s = check_hip(c, w->d_rt_resp.alloc((size_t)kSvoSelThreads * kSvoSelMaxE), "retain resp");
         if (!s) s = check_hip(c, w->d_rt_order.alloc((size_t)kSvoSelThreads * kSvoSelMaxE + 1), "retain order");
