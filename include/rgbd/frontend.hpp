@@ -93,8 +93,9 @@ public:
 };
 
 // Extractor(eType detector, eType descriptor, eMode mode) -- Features/Extractor.cpp:15-22.  The accelerated
-// pairs are (ORB2, ORB2), (SVO, BRIEF) (main.cpp:31 runs the latter), (GFTT, BRIEF) (cv::GFTTDetector, :178-181) and
-// (ORB, ORB) (cv::ORB as detector and descriptor, :163-166, 216-218) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode (createAdaptiveDetector, :82-109); the other OpenCV stock
+// pairs are (ORB2, ORB2), (SVO, BRIEF) (main.cpp:31 runs the latter), (GFTT, BRIEF) (cv::GFTTDetector, :178-181),
+// (FAST, BRIEF) and (FAST, ORB) (cv::FastFeatureDetector::create(), :168-171, with BRIEF or cv::ORB::create() as
+// descriptor) and (ORB, ORB) (cv::ORB as detector and descriptor, :163-166, 216-218) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode (createAdaptiveDetector, :82-109); the other OpenCV stock
 // detectors / descriptors and the other ADAPTIVE adjusters (GFTT, ORB, SURF, SIFT) are not on this path and throw.
 class Extractor : public ExtractorBase {
 public:
@@ -110,8 +111,9 @@ public:
         const bool adaptive = mode == ADAPTIVE && detector == FAST && descriptor == BRIEF;
         const bool gftt = detector == GFTT && descriptor == BRIEF;
         const bool cvorb = detector == ORB && descriptor == ORB;
-        if (!adaptive && (mode != NORMAL || !(orb2 || svo || gftt || cvorb)))
-            throw Error("Extractor: only (ORB2, ORB2), (SVO, BRIEF), (GFTT, BRIEF) and (ORB, ORB) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
+        const bool fast = detector == FAST && (descriptor == BRIEF || descriptor == ORB);
+        if (!adaptive && (mode != NORMAL || !(orb2 || svo || gftt || cvorb || fast)))
+            throw Error("Extractor: only (ORB2, ORB2), (SVO, BRIEF), (GFTT, BRIEF), (FAST, BRIEF), (FAST, ORB) and (ORB, ORB) in NORMAL mode and (FAST, BRIEF) in ADAPTIVE mode are accelerated");
         cam_ = cam;
         setParameters(1000, 1.2f, 8, 20, 7);   // :21
     }
@@ -129,6 +131,11 @@ public:
             // init()'s tables, which the getters below report
             rgbd_adaptive_params p{nfeatures, 600, 3, 3, 31, 5, 0, 0, 20.0, 2.0, 10000.0, 1.3, 0.7};
             s = rgbd_create_adaptive(device_, W_, H_, maxB_, &p, &cam_, &c);
+        } else if (mDetectorType == FAST) {
+            // cv::FastFeatureDetector::create(), :168-171: threshold 10, nonmaxSuppression, TYPE_9_16; the corner list
+            // at its largest (65536), the default output slack
+            rgbd_fast_params p{nfeatures, 10, mDescriptorType == ORB ? RGBD_FAST_ORB : RGBD_FAST_BRIEF, 65536, 0};
+            s = rgbd_create_fast(device_, W_, H_, maxB_, &p, &cam_, &c);
         } else if (mDetectorType == GFTT) {
             // GFTTDetector::create(nfeatures, 0.01, 3, 3, false, 0.04), :178-181: nfeatures is maxCorners
             rgbd_gftt_params p{nfeatures, 0, 0.01, 3.0};
@@ -175,7 +182,7 @@ public:
         for (float& v : f) v = 1.0f / v;
         return f;
     }
-    // OpenCV's own BRIEF tests (opencv_contrib generated_32.i), 256 x {y1, x1, y2, x2}; SVO, GFTT and ADAPTIVE contexts only
+    // OpenCV's own BRIEF tests (opencv_contrib generated_32.i), 256 x {y1, x1, y2, x2}; SVO, GFTT, (FAST, BRIEF) and ADAPTIVE contexts only
     void setBriefPattern(const int8_t* pairs) { check(ctx_.get(), rgbd_svo_set_brief_pattern(ctx_.get(), pairs), "setBriefPattern"); }
 
     eType mDetectorType, mDescriptorType;

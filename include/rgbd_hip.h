@@ -302,6 +302,45 @@ rgbd_status rgbd_create_cvorb(int device, int width, int height, int max_batch, 
 rgbd_status rgbd_cvorb_debug_level(rgbd_ctx* ctx, int32_t b, int32_t level, int32_t stage, int32_t* xys, float* harris,
                                    int32_t cap, int32_t* n);
 
+/* ------------------------------------------------------------------ plain FAST extractor */
+/* Extractor(FAST, BRIEF | ORB, NORMAL) (Features/Extractor.cpp:50-61, 168-171, 216-218, 224-226): cv::FastFeatureDetector::create()
+ * over the whole image (cv::FAST(gray, threshold, nonmaxSuppression = true, TYPE_9_16), corners in [3, W - 3) x
+ * [3, H - 3) in raster order, response = cornerScore<16>), retainBest(nfeatures) when there are more than nfeatures
+ * corners (nth_element at nfeatures - 1, then every tie of the boundary response, in libstdc++'s element order),
+ * then the descriptor.  RGBD_FAST_BRIEF: cv::xfeatures2d::BriefDescriptorExtractor (32 bytes, runByImageBorder(28));
+ * rgbd_svo_set / get_brief_pattern work on such a context.  RGBD_FAST_ORB: cv::ORB::create()->compute() on the
+ * provided keypoints: runByImageBorder(31), one level (every octave is 0), the 7x7 sigma-2 blur, the 256 tests of
+ * bit_pattern_31_ steered by the keypoint's own angle, which compute() does not recompute: every descriptor is
+ * steered by -1 degree; the BRIEF table entry points refuse such a context.  Keypoints: size 7, angle -1,
+ * response = the FAST score, octave 0, class_id -1.  DESIGN.md, "Plain FAST definition"; tests/fast_model.py.  No
+ * frame-to-frame state.
+ * RGBD_ERR_UNSUPPORTED before any allocation: the refusals of a one-level ORB geometry (as for
+ * rgbd_create_adaptive), sides above 2047 px, nfeatures outside 1..12288, threshold outside 1..255, a descriptor
+ * other than the two named, cand_cap outside 0..65536, max_keypoints nonzero and outside nfeatures..65536. */
+enum { RGBD_FAST_BRIEF = 0, RGBD_FAST_ORB = 1 };
+typedef struct {
+    int32_t nfeatures;        /* 1000: retainBest(nfeatures) (Extractor::setParameters) */
+    int32_t threshold;        /* 10 (cv::FastFeatureDetector::create()'s default); 1..255 */
+    int32_t descriptor;       /* RGBD_FAST_BRIEF | RGBD_FAST_ORB */
+    int32_t cand_cap;         /* corners stored per frame before retainBest; 0: 32768, at most 65536 (a uniform-noise
+                                 640 x 480 frame has 31,337).  A frame with more fails alone with RGBD_ERR_CAPACITY */
+    int32_t max_keypoints;    /* output capacity per frame; 0: nfeatures + nfeatures / 4.  retainBest keeps every tie of
+                                 its boundary response; a frame that keeps more than this (before the descriptor's
+                                 border filter) fails alone with RGBD_ERR_CAPACITY */
+} rgbd_fast_params;
+rgbd_status rgbd_create_fast(int device, int width, int height, int max_batch, const rgbd_fast_params* params,
+                             const rgbd_camera* cam, rgbd_ctx** out);
+/* Frame b of the last batch: *n_candidates = the corners cv::FAST found (the count goes on past cand_cap), and the
+ * stored ones in raster order, before retainBest, as xys[3 i ..] = (x, y, score); *n = how many were stored.  xys may
+ * be null to read the counts only; cap = entries it holds (RGBD_ERR_CAPACITY when the list is longer).  On another
+ * kind of context: RGBD_ERR_ARG, "not a FAST context". */
+rgbd_status rgbd_fast_debug_corners(rgbd_ctx* ctx, int32_t b, int32_t* n_candidates, int32_t* xys, int32_t cap, int32_t* n);
+/* The device retainBest of k_fast_select (both of its tiers: global scratch above 12288 live elements, LDS below) on
+ * n host responses (n <= 65536): order[0..m) = the retained original indices in cv::KeyPointsFilter's order.
+ * depth_limit as for rgbd_svo_retain_best. */
+rgbd_status rgbd_fast_retain_best(rgbd_ctx* ctx, const float* resp, int32_t n, int32_t n_points, int32_t depth_limit,
+                                  int32_t* order, int32_t* m);
+
 /* ------------------------------------------------------------------ matching */
 /* BFMatcher(NORM_HAMMING).knnMatch(k=2) (Features/Matcher.cpp:113): out[q] = {d1, i1, d2, i2}.
  * At most 65536 train rows (nt): the kernel's rank key holds the train index in 16 bits.  A larger nt

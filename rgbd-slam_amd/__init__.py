@@ -112,6 +112,24 @@ def cvorb_params(nfeatures=1000, scale_factor=1.2, nlevels=8, edge_threshold=31,
     return CvorbParams(nfeatures, scale_factor, nlevels, edge_threshold, fast_threshold, cand_cap, max_keypoints)
 
 
+class FastParams(C.Structure):
+    """rgbd_fast_params: Extractor(FAST, BRIEF | ORB, NORMAL) (Features/Extractor.cpp:168-171, 216-218, 224-226)."""
+    _fields_ = [("nfeatures", C.c_int32), ("threshold", C.c_int32), ("descriptor", C.c_int32), ("cand_cap", C.c_int32),
+                ("max_keypoints", C.c_int32)]
+
+
+FAST_BRIEF, FAST_ORB = 0, 1
+
+
+def fast_params(nfeatures=1000, threshold=10, descriptor="brief", cand_cap=0, max_keypoints=0) -> FastParams:
+    """cv::FastFeatureDetector::create()'s values (threshold 10, nonmaxSuppression, TYPE_9_16).  descriptor "brief"
+    (BriefDescriptorExtractor) or "orb" (cv::ORB::create()->compute()); cand_cap 0 = 32768 stored corners per frame,
+    at most 65536; max_keypoints 0 = nfeatures + nfeatures / 4 (retainBest keeps ties).  A frame over either raises
+    RGBD_ERR_CAPACITY for that frame alone."""
+    d = {"brief": FAST_BRIEF, "orb": FAST_ORB}.get(descriptor, descriptor)
+    return FastParams(nfeatures, threshold, int(d), cand_cap, max_keypoints)
+
+
 class CloudParams(C.Structure):
     _fields_ = [("stride", C.c_int32), ("zmin", C.c_float), ("zmax", C.c_float), ("leaf", C.c_float),
                 ("sor_k", C.c_int32), ("sor_std", C.c_double)]
@@ -221,6 +239,10 @@ _SIGS = {
     "rgbd_create_cvorb": (_i32, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CvorbParams), C.POINTER(Camera),
                                  C.POINTER(_vp)]),
     "rgbd_cvorb_debug_level": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _PI]),
+    "rgbd_create_fast": (_i32, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FastParams), C.POINTER(Camera),
+                                C.POINTER(_vp)]),
+    "rgbd_fast_debug_corners": (_i32, [_vp, _i32, _PI, _vp, _i32, _PI]),
+    "rgbd_fast_retain_best": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _PI]),
     "rgbd_destroy": (None, [_vp]),
     "rgbd_last_error": (C.c_char_p, [_vp]),
     "rgbd_max_keypoints": (_i32, [_vp]),
@@ -446,22 +468,26 @@ class Context:
     def __init__(self, width=640, height=480, max_batch=1, orb: OrbParams | None = None,
                  cam: Camera | None = None, device=0, svo: SvoParams | None = None,
                  adaptive: AdaptiveParams | None = None, gftt: GfttParams | None = None,
-                 cvorb: CvorbParams | None = None):
+                 cvorb: CvorbParams | None = None, fast: FastParams | None = None):
         """svo: an Extractor(SVO, BRIEF, NORMAL) context (rgbd_create_svo) instead of the ORBextractor;
         adaptive: an Extractor(FAST, BRIEF, ADAPTIVE) context (rgbd_create_adaptive);
         gftt: an Extractor(GFTT, BRIEF, NORMAL) context (rgbd_create_gftt);
-        cvorb: an Extractor(ORB, ORB, NORMAL) context, OpenCV's ORB (rgbd_create_cvorb)."""
-        if (svo is not None) + (adaptive is not None) + (gftt is not None) + (cvorb is not None) > 1:
-            raise ValueError("Context: svo, adaptive, gftt and cvorb are different extractors; give one")
+        cvorb: an Extractor(ORB, ORB, NORMAL) context, OpenCV's ORB (rgbd_create_cvorb);
+        fast: an Extractor(FAST, BRIEF | ORB, NORMAL) context (rgbd_create_fast)."""
+        if (svo is not None) + (adaptive is not None) + (gftt is not None) + (cvorb is not None) + (fast is not None) > 1:
+            raise ValueError("Context: svo, adaptive, gftt, cvorb and fast are different extractors; give one")
         self.orb = orb or orb_params()
         self.cam = cam or camera(535.4, 539.2, 320.1, 247.6)
         self.svo = svo
         self.adaptive = adaptive
         self.gftt = gftt
         self.cvorb = cvorb
+        self.fast = fast
         self.W, self.H = width, height
         h = C.c_void_p()
-        if cvorb is not None:
+        if fast is not None:
+            st = lib().rgbd_create_fast(device, width, height, max_batch, C.byref(fast), C.byref(self.cam), C.byref(h))
+        elif cvorb is not None:
             st = lib().rgbd_create_cvorb(device, width, height, max_batch, C.byref(cvorb), C.byref(self.cam), C.byref(h))
         elif gftt is not None:
             st = lib().rgbd_create_gftt(device, width, height, max_batch, C.byref(gftt), C.byref(self.cam), C.byref(h))
@@ -623,7 +649,26 @@ class Context:
         out["s2"], out["h2"] = xys[:n.value].copy(), hr[:n.value].copy()
         return out
 
-    # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive and GFTT contexts)
+    # --- plain FAST (rgbd_create_fast contexts)
+    def fast_debug_corners(self, b: int):
+        """Frame b of the last batch: (the corners cv::FAST found, counted past cand_cap; the stored ones [m, 3] int32
+        (x, y, score) in raster order, before retainBest)."""
+        nc, n = C.c_int32(0), C.c_int32(0)
+        self._check(lib().rgbd_fast_debug_corners(self._h, b, C.byref(nc), None, 0, C.byref(n)), "fast_debug_corners")
+        xys = np.zeros((max(n.value, 1), 3), np.int32)
+        self._check(lib().rgbd_fast_debug_corners(self._h, b, C.byref(nc), _ptr(xys), len(xys), C.byref(n)), "fast_debug_corners")
+        return nc.value, xys[:n.value].copy()
+
+    def fast_retain_best(self, resp: np.ndarray, n_points: int, depth_limit: int = -1) -> np.ndarray:
+        """The device retainBest(n_points) of k_fast_select on up to 65536 responses: the kept original indices in order."""
+        resp = np.ascontiguousarray(resp, dtype=np.float32)
+        order = np.zeros(max(len(resp), 1), np.int32)
+        m = C.c_int32(0)
+        self._check(lib().rgbd_fast_retain_best(self._h, _ptr(resp), len(resp), n_points, depth_limit, _ptr(order), C.byref(m)),
+                    "fast_retain_best")
+        return order[:m.value].copy()
+
+    # --- SVO + BRIEF (rgbd_create_svo contexts; the BRIEF table also on adaptive, GFTT and (FAST, BRIEF) contexts)
     def set_brief_pattern(self, pairs: np.ndarray):
         pairs = np.ascontiguousarray(pairs, dtype=np.int8).reshape(256, 4)
         self._check(lib().rgbd_svo_set_brief_pattern(self._h, _ptr(pairs)), "set_brief_pattern")

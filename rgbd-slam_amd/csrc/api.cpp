@@ -219,7 +219,7 @@ rgbd_status upload_table(rgbd_ctx* c, DevBuf<D>& d, const std::vector<T>& v, con
 
 rgbd_status create_ctx(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
                        const rgbd_svo_params* svo, const rgbd_adaptive_params* adp, const rgbd_gftt_params* gftt,
-                       const rgbd_cvorb_params* cvorb, const rgbd_camera* cam, rgbd_ctx** out)
+                       const rgbd_cvorb_params* cvorb, const rgbd_fast_params* fast, const rgbd_camera* cam, rgbd_ctx** out)
 {
     if (!out || !orb || !cam || max_batch < 1) return RGBD_ERR_ARG;
     rgbd_ctx* c = new rgbd_ctx();
@@ -245,6 +245,10 @@ rgbd_status create_ctx(int device, int width, int height, int max_batch, const r
     if (cvorb) {
         const rgbd_status sc = cvorb_check_params(c, *cvorb);
         if (sc) return sc;
+    }
+    if (fast) {
+        const rgbd_status sf = fast_configure(c, *fast);   // as the adaptive extractor's
+        if (sf) return sf;
     }
     if (s) return s;
     if (svo && (s = svo_configure(c, *svo))) return s;   // sets cfg.kp_cap before the allocations
@@ -308,7 +312,7 @@ extern "C" {
 rgbd_status rgbd_create(int device, int width, int height, int max_batch, const rgbd_orb_params* orb,
                         const rgbd_camera* cam, rgbd_ctx** out)
 {
-    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, orb, nullptr, nullptr, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, const rgbd_svo_params* svo,
@@ -319,7 +323,7 @@ rgbd_status rgbd_create_svo(int device, int width, int height, int max_batch, co
     // fields only shape the scale tables the reference's getters report (the ORB workspace is never run,
     // so its budget is kept small)
     const rgbd_orb_params orb{std::max(1, std::min(svo->nfeatures, 1000)), 1.2f, 8, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, svo, nullptr, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batch, const rgbd_adaptive_params* params,
@@ -329,7 +333,7 @@ rgbd_status rgbd_create_adaptive(int device, int width, int height, int max_batc
     // the ORB workspace is never run: a one-level ORB geometry (every adaptive keypoint has octave 0), so of the
     // ORB shape refusals only level 0's remain (the 8-level geometry refuses e.g. 320 x 256 for its level 7)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, nullptr, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, params, nullptr, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, const rgbd_gftt_params* params,
@@ -338,7 +342,7 @@ rgbd_status rgbd_create_gftt(int device, int width, int height, int max_batch, c
     if (!params) return RGBD_ERR_ARG;
     // as for rgbd_create_adaptive: a one-level ORB geometry that is never run (every GFTT keypoint has octave 0)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, params, nullptr, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, params, nullptr, nullptr, cam, out);
 }
 
 rgbd_status rgbd_create_cvorb(int device, int width, int height, int max_batch, const rgbd_cvorb_params* params,
@@ -348,7 +352,17 @@ rgbd_status rgbd_create_cvorb(int device, int width, int height, int max_batch, 
     // the ORB geometry of the caller's pyramid: its k_pyramid and blur run; its FAST cells and quadtree never do, so
     // their budget is kept small (as for rgbd_create_svo)
     const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), params->scale_factor, params->nlevels, 20, 7};
-    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, nullptr, params, cam, out);
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, nullptr, params, nullptr, cam, out);
+}
+
+rgbd_status rgbd_create_fast(int device, int width, int height, int max_batch, const rgbd_fast_params* params,
+                             const rgbd_camera* cam, rgbd_ctx** out)
+{
+    if (!params) return RGBD_ERR_ARG;
+    // as for rgbd_create_adaptive: a one-level ORB geometry (every FAST keypoint has octave 0); the ORB descriptor runs its
+    // gray level and blur, the BRIEF descriptor nothing of it
+    const rgbd_orb_params orb{std::max(1, std::min(params->nfeatures, 1000)), 1.2f, 1, 20, 7};
+    return create_ctx(device, width, height, max_batch, &orb, nullptr, nullptr, nullptr, nullptr, params, cam, out);
 }
 
 void rgbd_destroy(rgbd_ctx* c)

@@ -1,4 +1,4 @@
-// brief_front.cpp -- the shared head and tail of the SVO, adaptive and GFTT extractions (brief_front.h).
+// brief_front.cpp -- the shared head and tail of the SVO, adaptive, GFTT and FAST + BRIEF extractions (brief_front.h).
 #include "brief_front.h"
 
 #include <cstring>
@@ -28,7 +28,7 @@ BriefFront* brief_of(rgbd_ctx* c) { return c->front ? c->front->brief() : nullpt
 
 rgbd_status no_brief(rgbd_ctx* c)
 {
-    return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive or GFTT context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt)");
+    return fail(c, RGBD_ERR_ARG, "not an SVO, adaptive, GFTT or FAST + BRIEF context (rgbd_create_svo, rgbd_create_adaptive, rgbd_create_gftt, rgbd_create_fast)");
 }
 
 }  // namespace

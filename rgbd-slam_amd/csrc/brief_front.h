@@ -1,4 +1,4 @@
-// brief_front.h -- what the SVO, adaptive and GFTT front ends share around their detectors: k_svo_pyramid (gray,
+// brief_front.h -- what the SVO, adaptive, GFTT and FAST + BRIEF front ends share around their detectors: k_svo_pyramid (gray,
 // halfSample levels, 9x9 box sums) as the head of an extraction, k_svo_brief + k_undistort as its tail, and the
 // BRIEF-32 test table behind rgbd_svo_set / get_brief_pattern.
 #pragma once

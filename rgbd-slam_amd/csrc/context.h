@@ -130,6 +130,8 @@ rgbd_status fail(rgbd_ctx* c, rgbd_status code, const std::string& msg);
 // what a frame's extraction flag (rgbd_ctx::d_err, nonzero) says, for RGBD_ERR_CAPACITY: one wording on every path
 inline const char* extract_flag_message(int flag)
 {
+    if (flag & 128) return "FAST: keypoints kept by retainBest exceed max_keypoints (retainBest keeps ties)";
+    if (flag & 64) return "FAST: the frame has more corners than cand_cap stores";
     if (flag & 32) return "cv::ORB: the frame keeps more keypoints than max_keypoints (retainBest keeps ties)";
     if (flag & 16) return "cv::ORB: a level has more FAST corners than cand_cap stores";
     if (flag & 8) return "gftt: the frame has more candidates than cand_cap stores";
@@ -171,6 +173,7 @@ rgbd_status run_orb_pyramid(rgbd_ctx* c, const uint8_t* d_bgr, int B, bool from_
 rgbd_status svo_configure(rgbd_ctx* c, const rgbd_svo_params& p);             // svo_host.cpp
 rgbd_status adaptive_configure(rgbd_ctx* c, const rgbd_adaptive_params& p);   // adaptive_host.cpp
 rgbd_status gftt_configure(rgbd_ctx* c, const rgbd_gftt_params& p);           // gftt_host.cpp
+rgbd_status fast_configure(rgbd_ctx* c, const rgbd_fast_params& p);           // fast_host.cpp
 rgbd_status cvorb_check_params(rgbd_ctx* c, const rgbd_cvorb_params& p);      // cvorb_host.cpp: the parameter refusals, before the geometry's
 rgbd_status cvorb_configure(rgbd_ctx* c, const rgbd_cvorb_params& p);         // on an accepted geometry
 }  // namespace rgbd

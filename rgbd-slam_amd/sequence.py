@@ -40,7 +40,9 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
       - "svo": SVO + BRIEF, the reference's default;
       - "adaptive": FAST + BRIEF, ADAPTIVE;
       - "gftt": Shi-Tomasi GFTT + BRIEF, NORMAL (no state between frames);
-      - "cvorb": Extractor(ORB, ORB, NORMAL), OpenCV's ORB (no state between frames; cand_cap at its bound).
+      - "cvorb": Extractor(ORB, ORB, NORMAL), OpenCV's ORB (no state between frames; cand_cap at its bound);
+      - "fast" / "fast-orb": Extractor(FAST, BRIEF, NORMAL) / Extractor(FAST, ORB, NORMAL) (no state between frames;
+        cand_cap at its bound).
     The adaptive extractor's per-cell thresholds are state: before every later batch they are rewound on the device by the batches' overlap (1 frame with pnp, 2 with se3), so the
     frames a batch repeats start from the thresholds they started from the first time."""
     import torch
@@ -61,8 +63,11 @@ def track_sequence(pkg, ds, B: int = 64, solver: str = "pnp", nfeatures: int = 1
     elif extractor == "cvorb":
         ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device,
                           cvorb=pkg.cvorb_params(nfeatures, cand_cap=12288))
+    elif extractor in ("fast", "fast-orb"):
+        ctx = pkg.Context(ds.W, ds.H, max_batch=B, cam=c, device=device,
+                          fast=pkg.fast_params(nfeatures, descriptor="orb" if extractor == "fast-orb" else "brief", cand_cap=65536))
     else:
-        raise ValueError(f"extractor must be 'orb', 'svo', 'adaptive', 'gftt' or 'cvorb', not {extractor!r}")
+        raise ValueError(f"extractor must be 'orb', 'svo', 'adaptive', 'gftt', 'cvorb', 'fast' or 'fast-orb', not {extractor!r}")
     adaptive = extractor == "adaptive"
     dev = torch.device("cuda", device)
     poses = np.zeros((n, 4, 4), np.float32)

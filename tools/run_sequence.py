@@ -21,9 +21,9 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--solver", choices=["pnp", "se3"], default="pnp")
     ap.add_argument("--nfeatures", type=int, default=1000)
-    ap.add_argument("--extractor", choices=["orb", "svo", "adaptive", "gftt", "cvorb"], default="orb",
-                    help="ORB2 (default), SVO + BRIEF, the adaptive FAST + BRIEF extractor, Shi-Tomasi GFTT + BRIEF, or "
-                         "OpenCV's ORB")
+    ap.add_argument("--extractor", choices=["orb", "svo", "adaptive", "gftt", "cvorb", "fast", "fast-orb"], default="orb",
+                    help="ORB2 (default), SVO + BRIEF, the adaptive FAST + BRIEF extractor, Shi-Tomasi GFTT + BRIEF, "
+                         "OpenCV's ORB, or plain FAST with BRIEF or ORB descriptors")
     ap.add_argument("--max-frames", type=int, default=None)
     ap.add_argument("--out", default="CameraTrajectory.txt")
     ap.add_argument("--posegraph", action="store_true",
